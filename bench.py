@@ -21,9 +21,16 @@ Correctness gate (fails a kernel that writes nothing or wrong bytes inside the t
 before the timed region, every batch's rows that its first timed operation writes are zeroed
 (parity before an encode, rows 0-3 before a reconstruct); after it, every row must equal the
 golden codeword (data from the seeded generator, parity from the first encode, which the CPU leg
-checks against the klauspost-strategy CPU port on stripe 0).
+of a --full run checks against the klauspost-strategy CPU port on stripe 0).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: it builds the batches, settles and warms up, times
+the K steps, checks the gate, writes the last step's outputs if --dump-outputs is given (see
+dump_outputs) and prints the result line.  --full adds everything else to the same line, as before:
+the rocprofv3 counter passes for the roofline's traffic, strong scaling, the per-operation figures,
+BASELINE configs 1/4/5 with their CPU baselines, the multi-GPU repair leg, segment latency, the host
+path and the headline's CPU baseline (several minutes; --no-cpu / --no-pmc / --no-extra trim it).
 
 --gpus N > 1 without a torch.distributed environment re-launches this script under
 `python -m torch.distributed.run --nproc-per-node N` as a child process (before this process
@@ -66,11 +73,17 @@ def parse():
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--stripes", type=int, default=8, help="stripes per batch (per GPU per operation)")
     p.add_argument("--shard-size", type=int, default=S_DEFAULT)
-    p.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline sample length")
-    p.add_argument("--op-seconds", type=float, default=1.5, help="device time per isolated-operation figure")
-    p.add_argument("--no-cpu", action="store_true")
-    p.add_argument("--no-pmc", action="store_true")
-    p.add_argument("--no-extra", action="store_true", help="skip the secondary per-operation figures")
+    p.add_argument("--full", action="store_true",
+                   help="also run everything beside the headline: PMC traffic of the step kernel, strong scaling, "
+                        "the per-operation figures, BASELINE configs 1/4/5, segment latency, the host path and the "
+                        "CPU baselines (minutes; a plain run only sets up, warms up, times the steps and prints)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step computed as DIR/<name>.npy")
+    p.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline sample length (--full)")
+    p.add_argument("--op-seconds", type=float, default=1.5, help="device time per isolated-operation figure (--full)")
+    p.add_argument("--no-cpu", action="store_true", help="with --full: skip the CPU baselines")
+    p.add_argument("--no-pmc", action="store_true", help="with --full: skip the rocprofv3 counter passes")
+    p.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary per-operation figures")
     p.add_argument("--graph", action="store_true", help="replay each step as a captured HIP graph")
     p.add_argument("--settle-ms", type=float, default=2000.0, help="untimed load before warmup (clock ramp)")
     p.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
@@ -250,6 +263,42 @@ def leg(name, fn):
 
 EXIT_GATE_FAILED = 3
 
+DUMP_BLOCK = 4096  # bytes per block of the *_blocksum arrays
+DUMP_SAMPLE = 1 << 21  # byte positions per *_sample array
+DUMP_SEED = 0xCF5ED0
+
+
+def dump_outputs(out_dir, torch, batch, last, S, rank, world):
+    """--dump-outputs: what the last timed step (step index `last`) handed back to its caller -- the
+    four parity rows of every stripe of the batch it encoded (`encode_parity`) and the rebuilt rows
+    0-3 of every stripe of the batch it reconstructed (`reconstruct_rows`), each (stripes, 4, S)
+    bytes.  That is 179 MB per array at the default shapes, so each is stored in two reduced forms:
+      <name>_blocksum.npy  float64 (stripes, 4, ceil(S / 4096)): the sum of every 4096-byte block of
+                           every row -- exact, and every output byte is in one of them
+      <name>_sample.npy    float32 (2^21,): the bytes at fixed positions of the flattened array
+                           (numpy default_rng(DUMP_SEED + array number), sorted)
+    The inputs are seeded and `last` depends only on --warmup and --steps (the settle phase runs whole
+    rotations), so two builds run with the same arguments write comparable files.  With more than one
+    rank every rank writes its own, suffixed _rank<r>."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    outs = (("encode_parity", batch[last % NBATCH, :, K_DATA:, :S]),
+            ("reconstruct_rows", batch[(last + 2) % NBATCH, :, ERASED[0]:ERASED[-1] + 1, :S]))
+    for n, (name, rows) in enumerate(outs):
+        nst, nrow, _ = rows.shape
+        nblk = -(-S // DUMP_BLOCK)
+        padded = torch.zeros((nst, nrow, nblk * DUMP_BLOCK), dtype=torch.uint8, device=rows.device)
+        padded[:, :, :S] = rows
+        sums = padded.view(nst, nrow, nblk, DUMP_BLOCK).sum(dim=3, dtype=torch.float64)
+        np.save(os.path.join(out_dir, f"{name}_blocksum{suffix}.npy"), sums.cpu().numpy())
+        flat = padded[:, :, :S].reshape(-1)
+        pos = np.sort(np.random.default_rng(DUMP_SEED + n).integers(0, flat.numel(), min(DUMP_SAMPLE, flat.numel())))
+        sample = flat[torch.from_numpy(pos).to(rows.device)].to(torch.float32)
+        np.save(os.path.join(out_dir, f"{name}_sample{suffix}.npy"), sample.cpu().numpy())
+        del padded, flat
+
 
 def main():
     args = parse()
@@ -262,8 +311,8 @@ def main():
         raise SystemExit(f"bench.py: --gpus {args.gpus} but WORLD_SIZE={world}")
     S, nst = args.shard_size, args.stripes
 
-    traffic, pmc_note = None, "skipped"
-    if rank == 0 and world == 1 and not args.no_pmc and not args.pmc_child:
+    traffic, pmc_note = None, "skipped" if args.full else "not collected (a --full run collects it)"
+    if args.full and rank == 0 and world == 1 and not args.no_pmc and not args.pmc_child:
         traffic, pmc_note = pmc_traffic(args)  # before this process touches the GPU
 
     import torch
@@ -332,7 +381,7 @@ def main():
         return
 
     golden = batch[:, :, :, :S].clone()
-    golden_stripe0 = golden[0, 0].cpu().numpy() if rank == 0 else None
+    golden_stripe0 = golden[0, 0].cpu().numpy() if rank == 0 and args.full else None  # for the CPU leg
     reconstruct(0)  # plans the reconstruct (inversion cache) before any timing or capture
     torch.cuda.synchronize()
     graph = None
@@ -399,46 +448,16 @@ def main():
     # both step launches are the same 12 -> 4 kernel moving the same algorithmic bytes
     avg_ms = ev0.elapsed_time(ev1) / (2 * args.steps)
 
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, torch, batch, step_no[0] - 1, S, rank, world)
+
     # correctness gate: every row the timed launches wrote is the golden codeword again
     for b in range(NBATCH):
         assert torch.equal(batch[b, :, :, :S], golden[b]), f"batch {b} differs from the golden codeword after the timed steps"
     gate = {"zeroed_before_timed": {str(b): op for b, op in sorted(first.items())}, "rows_equal_golden": True}
 
-    # Strong scaling: the same nst-stripe total split over the ranks -- each codes the
-    # first ceil(nst / world) stripes of its batches -- timed like the headline (barrier + sync on both
-    # sides, max over ranks).  At N = 1 it is the headline's work; the driver's curve is the weak one.
-    per_rank = max(1, -(-nst // world))
-    strong_steps = max(NBATCH, args.steps // NBATCH * NBATCH)
-
-    def strong_step(i):
-        enc.encode_batch(ptrs[i % NBATCH], S, per_rank, stream=stream)
-        enc.reconstruct_batch(ptrs[(i + 2) % NBATCH], S, per_rank, ERASED, stream=stream)
-
-    with torch.cuda.stream(stream):
-        for i in range(NBATCH):
-            strong_step(i)
-    if world > 1:
-        torch.distributed.barrier()
-    torch.cuda.synchronize()
-    ts0 = time.perf_counter()
-    with torch.cuda.stream(stream):
-        for i in range(strong_steps):
-            strong_step(i)
-    torch.cuda.synchronize()
-    if world > 1:
-        torch.distributed.barrier()
-    st_el = time.perf_counter() - ts0
-    if world > 1:
-        t = torch.tensor([st_el], dtype=torch.float64, device=dev)
-        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
-        st_el = float(t.item())
-    for b in range(NBATCH):
-        assert torch.equal(batch[b, :, :, :S], golden[b]), f"batch {b} differs from the golden codeword (strong run)"
-    strong = {"total_stripes": per_rank * world, "stripes_per_gpu": per_rank, "steps": strong_steps,
-              "value": round(2 * K_DATA * S * per_rank * world * strong_steps / st_el / 1e9, 2), "unit": "GB/s",
-              "ms_per_step": round(st_el / strong_steps * 1e3, 4),
-              "note": ("fixed total work (BASELINE configs[2] strong scaling): the 8-stripe batch split over the "
-                       "GPUs, same step as the headline; rows checked against the golden codeword afterwards")}
+    # everything below the headline runs only with --full
+    strong = strong_scaling(args, torch, enc, batch, golden, ptrs, stream, dev, world) if args.full else None
 
     data_bytes = K_DATA * S * nst
     launch_bytes = (K_DATA + M_PARITY) * S * nst  # algorithmic bytes per launch (read 12S + write 4S)
@@ -446,7 +465,7 @@ def main():
     value = 2 * data_bytes * world * args.steps / elapsed / 1e9
 
     extra = {}
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         extra = secondary(args, torch, enc, batch, ptrs, stream, S, nst, pitch, dev, launch_bytes, data_bytes)
         del batch, golden
         torch.cuda.empty_cache()
@@ -464,7 +483,7 @@ def main():
             torch.distributed.destroy_process_group()
         return
     cpu = None
-    if world == 1 and not args.no_cpu:
+    if args.full and world == 1 and not args.no_cpu:
         stripe0 = golden_stripe0
         cpu, parity_ok = cpu_baseline(S, args.cpu_seconds, stripe0[:K_DATA], stripe0[K_DATA:])
         assert parity_ok, "GPU golden parity of stripe 0 differs from the CPU port's"
@@ -476,6 +495,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": round(elapsed / args.steps * 1e3, 4),
         "higher_is_better": True,
         "scaling": "weak",
@@ -527,6 +547,45 @@ def main():
         print(f"bench: {len(GATE_FAILURES)} secondary gate(s) failed: "
               + "; ".join(f"{g['leg']}: {g['error']}" for g in GATE_FAILURES), file=sys.stderr, flush=True)
         sys.exit(EXIT_GATE_FAILED)
+
+
+def strong_scaling(args, torch, enc, batch, golden, ptrs, stream, dev, world):
+    """Strong scaling: the same nst-stripe total split over the ranks -- each codes the
+    first ceil(nst / world) stripes of its batches -- timed like the headline (barrier + sync on both
+    sides, max over ranks).  At N = 1 it is the headline's work; the driver's curve is the weak one."""
+    S, nst = args.shard_size, args.stripes
+    per_rank = max(1, -(-nst // world))
+    strong_steps = max(NBATCH, args.steps // NBATCH * NBATCH)
+
+    def strong_step(i):
+        enc.encode_batch(ptrs[i % NBATCH], S, per_rank, stream=stream)
+        enc.reconstruct_batch(ptrs[(i + 2) % NBATCH], S, per_rank, ERASED, stream=stream)
+
+    with torch.cuda.stream(stream):
+        for i in range(NBATCH):
+            strong_step(i)
+    if world > 1:
+        torch.distributed.barrier()
+    torch.cuda.synchronize()
+    ts0 = time.perf_counter()
+    with torch.cuda.stream(stream):
+        for i in range(strong_steps):
+            strong_step(i)
+    torch.cuda.synchronize()
+    if world > 1:
+        torch.distributed.barrier()
+    st_el = time.perf_counter() - ts0
+    if world > 1:
+        t = torch.tensor([st_el], dtype=torch.float64, device=dev)
+        torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+        st_el = float(t.item())
+    for b in range(NBATCH):
+        assert torch.equal(batch[b, :, :, :S], golden[b]), f"batch {b} differs from the golden codeword (strong run)"
+    return {"total_stripes": per_rank * world, "stripes_per_gpu": per_rank, "steps": strong_steps,
+            "value": round(2 * K_DATA * S * per_rank * world * strong_steps / st_el / 1e9, 2), "unit": "GB/s",
+            "ms_per_step": round(st_el / strong_steps * 1e3, 4),
+            "note": ("fixed total work (BASELINE configs[2] strong scaling): the 8-stripe batch split over the "
+                     "GPUs, same step as the headline; rows checked against the golden codeword afterwards")}
 
 
 def secondary(args, torch, enc, batch, ptrs, stream, S, nst, pitch, dev, launch_bytes, data_bytes):
