@@ -198,8 +198,9 @@ hipError_t launch_group_run(const Group& g, size_t t0, size_t t1, uint32_t* dfla
   return e != hipSuccess ? e : launch_matvec(b, s);
 }
 
-// A group whose product is a plain store of a shape the fused product + CRC kernels cover (gf_crc.hpp:
-// m <= 6, k in {6, 8, 12, 16, 18}, one length) and whose checksum words sit at one stride per task
+// A group whose product is a plain store the fused product + CRC kernels have a route for
+// (matvec_crc_route, kernels.hpp, asked for the very job launched here; one length) and whose checksum
+// words sit at one stride per task
 // (no index remap, no other task of the same bid writing that bid's words) runs as one fused launch:
 // the shards are checksummed from the registers the product already holds, instead of a second pass
 // that reads every row again (EC12P4 8 x 64 MiB: 130 + 123 us -> ~180 us).  Returns false when the
@@ -216,10 +217,10 @@ bool fused_crc_group(const Group& g, uint32_t* dcrc, size_t nwords, const std::m
   const size_t nt = g.tasks.size();
   if (!kOn || p.dy16 || p.nstore != m || m == 0 || nt == 0) return false;
   const uint64_t len = g.lens[0];
-  if (len == 0 || !matvec_crc_supported(k, m, len, p.rows.v.data())) return false;
+  if (len == 0) return false;
   const StripeTask* t0 = g.tasks[0];
   const int mode = t0->crc;  // 2: inputs and outputs, 1: the stored outputs only
-  if (mode == 0 || (m > 6 && mode != 2)) return false;  // m = 12 (EC6P10L2 encode): every shard checksummed
+  if (mode == 0) return false;
   int64_t cs = 0;
   for (size_t i = 0; i < nt; ++i) {
     const StripeTask* t = g.tasks[i];
@@ -244,6 +245,9 @@ bool fused_crc_group(const Group& g, uint32_t* dcrc, size_t nwords, const std::m
   job.in = g.in.data();
   job.out = g.out.data();
   job.mode = MatVecMode::kStore;
+  // the route of exactly this job (its slots, length and stripe count): a shape only the bit-sliced
+  // kernel covers has one with every shard checksummed (mode 2) and the tile counts in range only
+  if (!matvec_crc_accepts(job, (int)cs, slot.data())) return false;
   *st = hip_status(launch_matvec_crc(job, dcrc + t0->crc_word, (int)cs, slot.data(), s, false),
                    "launch_matvec_crc(batch)");
   if (std::getenv("CFSEC_TRACE_BATCH"))  // which groups fused, for tests

@@ -636,12 +636,17 @@ bool bs_plain_matches(int k, int m, const uint8_t* coef) {
   return false;
 }
 
+// ... within the kernel's range: one length, at most 64^3 tiles per row and 2^32 - 1 over the stripes
+// (launch_matvec keeps the fixed-K kernels for the rest)
+bool bs_plain_takes(const MatVecJob& job) {
+  if (job.len == 0 || job.lens || !bs_plain_matches(job.k, job.m, job.coef)) return false;
+  const uint64_t tps = (job.len + kBcTile - 1) / kBcTile;
+  return tps <= (uint64_t)kBcPow * kBcPow * kBcPow && tps * (uint64_t)std::max(job.nstripes, 1) <= 0xFFFFFFFFull;
+}
+
 hipError_t launch_bs_plain(const MatVecJob& job, hipStream_t st) {
   // (the caller has resolved the mode to a plain store: kStore, or kStoreVerify storing every row)
-  if (!bs_plain_matches(job.k, job.m, job.coef) || job.len == 0 || job.lens ||
-      (job.len + kBcTile - 1) / kBcTile > (uint64_t)kBcPow * kBcPow * kBcPow ||
-      (job.len + kBcTile - 1) / kBcTile * (uint64_t)std::max(job.nstripes, 1) > 0xFFFFFFFFull)
-    return hipErrorInvalidValue;
+  if (!bs_plain_takes(job)) return hipErrorInvalidValue;
   if (env_mask("CFSEC_TRACE_CRC", 0))
     std::fprintf(stderr, "cfsec: bs plain k=%d m=%d stripes=%d len=%llu\n", job.k, job.m, job.nstripes,
                  (unsigned long long)job.len);

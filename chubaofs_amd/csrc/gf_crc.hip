@@ -1,5 +1,6 @@
 // gf_crc.hip -- host side of the fused matvec + shard CRC32 kernels (device code: gf_crc.hpp).
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <map>
 #include <mutex>
@@ -198,48 +199,64 @@ static bool crc_lds12_on() {
   return v;
 }
 
-bool matvec_crc_supported(int k, int m, size_t len, const uint8_t* coef) {
-  // the fused kernels exist for the input counts of the code modes of SURVEY §8, m <= 6 outputs, and
-  // EC6P10L2's fused encode (6 x (10 dyadic + 2 local) rows)
-  if (m < 1 || len > 0xFFFFFFFFull - crcdev::kTile) return false;
-  if (bs_crc_matches(k, m, coef)) return true;  // the bit-sliced fused kernels (gf_bs_crc.hip)
-  const bool crc_k = k == 6 || k == 8 || k == 12 || k == 16 || k == 18;
-  if (!crc_k) return false;
-  if (m <= 6) return true;
-  if (k == 6 && m == 12 && crc_lds12_on()) return true;
-  if (k == 6 && m == 12 && coef) {
-    const DyPlan dp = dyadic_plan(coef, m, k);
-    return dp.B == 2 && dp.E == 2;
+// The one routing decision of the fused product + checksum kernels (kernels.hpp): host arithmetic on
+// the job's scalars, coef, slot and the masks above, no HIP calls.
+CrcRoute matvec_crc_route(const MatVecJob& job, int crc_stride, const int* slot) {
+  const int k = job.k, m = job.m;
+  if (job.mode != MatVecMode::kStore || k < 1 || m < 1 || job.len > 0xFFFFFFFFull - crcdev::kTile || !slot ||
+      crc_stride <= 0 || crc_stride > 256 || job.nstripes < 0 || !job.coef || !job.in || !job.out)
+    return CrcRoute::kNone;
+  const bool cin = slot[0] >= 0;
+  for (int i = 0; i < k + m; ++i) {
+    const bool want = i >= k || cin;
+    if (want && (slot[i] < 0 || slot[i] >= crc_stride)) return CrcRoute::kNone;
   }
-  return false;
+  // a code mode's bit-sliced network, checksums from its bit planes (gf_bs_crc.hip): only with the
+  // inputs checksummed and the tile counts in its range -- a shape nothing else covers (k = 3, 4, 10,
+  // 15, m > 6) has no route otherwise
+  if (bs_crc_takes(job, crc_stride, slot)) return CrcRoute::kBitSliced;
+  // the kernels of gf_crc.hpp: the input counts of the code modes of SURVEY §8, m <= 6 outputs
+  if (k != 6 && k != 8 && k != 12 && k != 16 && k != 18) return CrcRoute::kNone;
+  if (m <= 6) return crc_lds_on() && m <= 4 && k <= 16 ? CrcRoute::kLookup : CrcRoute::kVperm;
+  // EC6P10L2's fused encode (6 x (10 dyadic + 2 local) rows), instantiated with its inputs
+  // checksummed only (every shard, as Put does)
+  if (k == 6 && m == 12 && cin) {
+    if (crc_lds12_on()) return CrcRoute::kLookup;
+    const DyPlan dp = dyadic_plan(job.coef, m, k);
+    if (dp.B == 2 && dp.E == 2) return CrcRoute::kVperm;
+  }
+  return CrcRoute::kNone;
+}
+
+const char* crc_route_name(CrcRoute r) {
+  switch (r) {
+    case CrcRoute::kBitSliced: return "bit-sliced";
+    case CrcRoute::kLookup: return "lookup";
+    case CrcRoute::kVperm: return "v_perm";
+    default: return "none";
+  }
 }
 
 uint32_t crc32_shift_ones(size_t len) { return mulmod(xpow(8 * (int64_t)len), 0xFFFFFFFFu) ^ 0xFFFFFFFFu; }
 
 bool matvec_crc_accepts(const MatVecJob& job, int crc_stride, const int* slot) {
-  if (job.mode != MatVecMode::kStore || !matvec_crc_supported(job.k, job.m, job.len, job.coef) || !slot ||
-      crc_stride <= 0 || crc_stride > 256 || job.nstripes < 0 || !job.coef || !job.in || !job.out)
-    return false;
-  const bool cin = slot[0] >= 0;
-  for (int i = 0; i < job.k + job.m; ++i) {
-    const bool want = i >= job.k || cin;
-    if (want && (slot[i] < 0 || slot[i] >= crc_stride)) return false;
-  }
-  // EC6P10L2's fused encode is instantiated with its inputs checksummed only (every shard, as Put does)
-  return !(job.m > 6 && !cin);
+  return matvec_crc_route(job, crc_stride, slot) != CrcRoute::kNone;
 }
 
 hipError_t launch_matvec_crc(const MatVecJob& job, uint32_t* crc, int crc_stride, const int* slot,
                              hipStream_t stream, bool zero) {
-  if (!crc || !matvec_crc_accepts(job, crc_stride, slot)) return hipErrorInvalidValue;
+  const CrcRoute route = crc ? matvec_crc_route(job, crc_stride, slot) : CrcRoute::kNone;
+  if (route == CrcRoute::kNone) return hipErrorInvalidValue;
   const int k = job.k, m = job.m;
   const bool cin = slot[0] >= 0;
+  const char* tr = std::getenv("CFSEC_TRACE_CRC");  // read per call: tests turn it on mid-process
+  if (tr && *tr && std::strtoul(tr, nullptr, 0))
+    std::fprintf(stderr, "cfsec: crc route=%s k=%d m=%d cin=%d stripes=%d len=%llu\n", crc_route_name(route), k, m,
+                 (int)cin, job.nstripes, (unsigned long long)job.len);
   hipError_t e = zero ? hipMemsetAsync(crc, 0, sizeof(uint32_t) * (size_t)crc_stride * job.nstripes, stream)
                       : hipSuccess;
   if (e != hipSuccess || job.nstripes == 0 || job.len == 0) return e;
-  // EC6P10L2's fused LRC encode and EC12P4's encode with every shard checksummed: the bit-sliced
-  // network, checksums from its bit planes (gf_bs_crc.hip, round 6)
-  if (cin && bs_crc_takes(job, crc_stride, slot)) return launch_bs_crc(job, crc, crc_stride, slot, stream);
+  if (route == CrcRoute::kBitSliced) return launch_bs_crc(job, crc, crc_stride, slot, stream);
 
   GfCrcArgs a{};
   e = crc_device_tables(&a.tabs);
@@ -258,17 +275,13 @@ hipError_t launch_matvec_crc(const MatVecJob& job, uint32_t* crc, int crc_stride
 #define CFSEC_CRC_DY2 1  // A/B switch for the 2x2 form
 #endif
   int dy = dp.E == 0 && ((dp.B == 4 && m == 4) || (CFSEC_CRC_DY2 && dp.B == 2 && m == 6 && k == 6)) ? dp.B : 0;
-  if (k == 6 && m == 12 && dp.B == 2 && dp.E == 2) {  // EC6P10L2 fused encode + its 18 checksums
-    if (!cin) return hipErrorInvalidValue;             // (the only form instantiated: inputs checksummed)
-    dy = 2;
-  }
+  if (m == 12) dy = 2;  // EC6P10L2 fused encode + its 18 checksums (the route: that form, inputs checksummed)
   // m <= 4, k <= 16: the lookup-product kernel (gf_crc_lds_kernel; CFSEC_CRC_LDS=0 keeps the v_perm
   // kernels for A/B): EC12P4 8 x 64 MiB encode + 16 checksums 225-230 -> 200 us
   // (profiles/r03/crc_lds_ab*.txt)
-  if (crc_lds_on() && m <= 4 && k <= 16) dy = -1;
   // EC6P10L2's fused LRC encode + 18 checksums (C4) on the same lookup kernel with 16-byte entries
   // (round 6): C4's put batch 245 -> 211 us per call against the v_perm form (profiles/r06/c4_crc_lds12.txt)
-  if (crc_lds12_on() && k == 6 && m == 12 && cin) dy = -1;
+  if (route == CrcRoute::kLookup) dy = -1;
   // Workgroups per launch.  The v_perm kernels: ~1024, each folding ~11 tiles per row before its
   // per-thread basis epilogue (16 rows x 32 columns); 512 / 2048 / 4096 were 3-7 % slower
   // (profiles/r01/crc_wgs_sweep.txt).  The lookup kernel: exactly the resident count (its 48-64 KiB

@@ -149,6 +149,7 @@ hipError_t launch_bs_crc(const MatVecJob& job, uint32_t* crc, int crc_stride, co
 // The product alone on the same kernel (no checksums) for the wide LRC modes' fused encodes (EC6P6L9,
 // EC6P8L10): a kStore job whose coef equals their networks, any alignment and length
 bool bs_plain_matches(int k, int m, const uint8_t* coef);
+bool bs_plain_takes(const MatVecJob& job);  // ... and one length, the tile counts within the kernel's range
 hipError_t launch_bs_plain(const MatVecJob& job, hipStream_t st);
 
 // repair_dy16 on a GfArgs block (gf_dy16.hip); launch_dy16_repair (gf_kernels.hip) fills it.

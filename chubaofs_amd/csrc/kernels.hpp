@@ -106,12 +106,26 @@ hipError_t launch_crc32_to(const uint8_t* const* ptrs, size_t len, int n, uint32
 // checksum in device word crc[s * crc_stride + slot[i]] of stripe s.  slot[0] < 0 skips the inputs
 // (checksum the outputs only).  Every word of crc[0 .. nstripes*crc_stride) is zeroed first, so
 // words no row maps to read 0 (zero = false: the caller zeroed them; the kernel XORs into them).
-// Only for matvec_crc_supported shapes (k in {6,8,12,16,18}, m <= 6; and k = 6, m = 12 when coef is
-// EC6P10L2's fused LRC matrix: 10 rows of 2x2 dyadic blocks + 2 plain rows).
-bool matvec_crc_supported(int k, int m, size_t len, const uint8_t* coef = nullptr);
-// launch_matvec_crc takes exactly the jobs this accepts (a supported shape, kStore, checksum slots
-// inside [0, crc_stride) with crc_stride <= 256, the inputs checksummed where the only instantiated
-// form does so); callers route everything else to the product and the separate pass.
+//
+// Which fused kernel runs a job, decided in one place (gf_crc.hip).  A pure host function: no HIP
+// calls, it reads the job's scalar fields, coef, slot and the A/B masks (CFSEC_BS_CRC,
+// CFSEC_CRC_LDS, CFSEC_CRC_LDS12):
+//   kBitSliced  gf_bs_crc.hip: coef equals a code mode's network, the inputs checksummed too
+//               (slot[0] >= 0), at most 64^3 tiles of 2 KiB per row and 2^32 - 1 over the stripes
+//   kLookup     gf_crc_lds_kernel: k in {6, 8, 12, 16}, m <= 4; any 6 x 12 matrix with the inputs
+//               checksummed
+//   kVperm      the v_perm kernels: k in {6, 8, 12, 16, 18}, m <= 6; 6 x 12 of EC6P10L2's form (10
+//               rows of 2x2 dyadic blocks + 2 plain rows) with the inputs checksummed
+//   kNone       no fused kernel (every other input count -- 3, 4, 10, 15 -- without its network's
+//               conditions, m > 6, a mode other than kStore, slots outside [0, crc_stride),
+//               crc_stride > 256, len > 2^32 - 1 - 4096): the product and the separate pass
+enum class CrcRoute : int { kNone = 0, kBitSliced = 1, kLookup = 2, kVperm = 3 };
+CrcRoute matvec_crc_route(const MatVecJob& job, int crc_stride, const int* slot);
+const char* crc_route_name(CrcRoute r);  // "none", "bit-sliced", "lookup", "v_perm"
+// route != kNone.  launch_matvec_crc takes exactly the jobs this accepts, by construction: it
+// dispatches on the same matvec_crc_route answer; callers send everything else to the product and
+// the separate pass (launch_matvec + launch_crc32_to).  CFSEC_TRACE_CRC (read per call) prints
+// "cfsec: crc route=<name> k=.. m=.. cin=.. stripes=.. len=.." to stderr per launch_matvec_crc.
 bool matvec_crc_accepts(const MatVecJob& job, int crc_stride, const int* slot);
 hipError_t launch_matvec_crc(const MatVecJob& job, uint32_t* crc, int crc_stride, const int* slot,
                              hipStream_t stream, bool zero = true);

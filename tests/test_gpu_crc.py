@@ -4,8 +4,10 @@ CubeFS computes crc32.ChecksumIEEE of every shard right after Encode (access/str
 and of repaired shards (blobnode/work_shard_recover.go:335-342).  The GPU computes them inside the
 coding kernel; every word must equal zlib's CRC-32 (the same polynomial, preset and final inversion
 as Go's hash/crc32 IEEE) of the shard bytes, and the coded bytes must still match the oracle.
-Shapes outside the fused kernel's range (m > 6, k not a code-mode count) take the product + the
-standalone CRC kernel and must give the same words.
+Shapes without a fused kernel (matvec_crc_route == none: outputs-only checksums with m > 6 or k not
+in {6, 8, 12, 16, 18}; every shard checksummed with a matrix that is no code mode's network) take the
+product + the standalone CRC kernel and must give the same words.  tests/test_crc_route.py pins the
+routing table, tests/test_gpu_crc_routes.py every route's bytes and words.
 """
 import zlib
 
@@ -17,8 +19,11 @@ from oracle import oracle as O
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-# (12, 4) (8, 1) (16, 4) (6, 3) (8, 2) (16, 3) (12, 1): the lookup-product fused kernel (m <= 4, k <= 16);
-# (6, 6) (18, 1): the v_perm fused kernels; (6, 10) (10, 4) (16, 20): product + standalone CRC
+# Encode (every shard checksummed), default masks: (12, 4) (6, 6) (16, 4) (6, 10) (10, 4) (16, 20): the
+# code modes' bit-sliced networks; (8, 1) (6, 3) (8, 2) (16, 3) (12, 1): the lookup-product fused kernel
+# (m <= 4, k <= 16); (18, 1): the v_perm fused kernel.  Reconstruct (the rebuilt shards only): lookup /
+# v_perm for k in {6, 8, 12, 16, 18} with m <= 6, product + standalone CRC for the rest ((6, 10) with
+# more than 6 rebuilt, (10, 4), (16, 20))
 SHAPES = [(12, 4), (6, 6), (8, 1), (18, 1), (16, 4), (6, 10), (10, 4), (16, 20), (6, 3), (8, 2), (16, 3), (12, 1)]
 SIZES = [1, 15, 16, 17, 4095, 4096, 4097, 8191, 65539, 174763]
 
