@@ -1027,7 +1027,7 @@ hipError_t launch_bs16_repair(int nd, int ne, const uint8_t* missing, const uint
                  : launch_rep_m<20, 0>(nd, a, r, grid, tps, (uint32_t)ntiles, st);
 }
 
-int bs_tab_stripes(int mo) { return kBsTabWords / (kBsK + mo); }
+static int bs_tab_stripes(int mo) { return kBsTabWords / (kBsK + mo); }
 
 // The row-offset tables (TAB 2: any number of stripes in one launch): a ring of kBsDevTables per
 // device, each slot a table in mapped, coherent host memory that the kernel reads directly (no copy
@@ -1144,7 +1144,7 @@ hipError_t launch_bs16_repair_tab(int nd, int ne, const uint8_t* missing, const 
     lo = std::min(lo, (uintptr_t)rows[i]);
     hi = std::max(hi, (uintptr_t)rows[i]);
   }
-  if (hi - lo > 0xFFFFFFFFull) return hipSuccess;  // not ok: the caller keeps its route
+  if (!bs_tab_span_ok(lo, hi)) return hipSuccess;  // not ok: the caller keeps its route
   *ok = true;
   BsRepairArgs r{};
   if (!rep_args(nd, missing, prow, ainv, r)) return hipErrorOutOfMemory;
@@ -1208,7 +1208,7 @@ hipError_t launch_bs_tab(int k, int m, const dev::GfArgs& a, const uint8_t* cons
     lo = std::min(lo, (uintptr_t)rows[i]);
     hi = std::max(hi, (uintptr_t)rows[i]);
   }
-  if (hi - lo > 0xFFFFFFFFull) return hipSuccess;  // not ok: the caller keeps its route
+  if (!bs_tab_span_ok(lo, hi)) return hipSuccess;  // not ok: the caller keeps its route
   BsDevTables* ring = dev_tables();
   if (!ring) return hipSuccess;
   std::lock_guard<std::mutex> lk(ring->mu);

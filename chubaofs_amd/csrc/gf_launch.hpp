@@ -125,12 +125,14 @@ hipError_t launch_bs16_repair(int nd, int ne, const uint8_t* missing, const uint
 // The same for stripes at unrelated addresses (every shard its own buffer): rows[s * (16 + mo) + i]
 // (the 16 inputs, then the mo = nd + 20 + ne outputs of stripe s) for ns stripes, every pointer
 // 16-byte aligned; a's other fields (flags, zw, pstore / pcmp, src) as for launch_bs16_repair.  The
-// rows go into the launch as 32-bit offsets from the lowest address, kBsTabStripes(mo) stripes per
-// launch; false in *ok when the rows span 4 GiB or more (the caller keeps its route).
-int bs_tab_stripes(int mo);
+// rows go into the launch as 32-bit offsets from the lowest address (through a device table, else an
+// argument block's worth of stripes per launch); false in *ok when the rows span 4 GiB or more
+// (plan_dy16_repair never sends such rows: it asks the same bs_tab_span_ok).
+constexpr bool bs_tab_span_ok(uintptr_t lo, uintptr_t hi) { return hi - lo <= 0xFFFFFFFFull; }
 // launch_bs for stripes at unrelated addresses: rows[s * (k + m) + i] (inputs, then outputs), any
 // number of stripes in one launch through a device copy of their 32-bit offsets; *ok false when the
-// rows span 4 GiB or more or the table cannot be had (the caller keeps its route)
+// rows span 4 GiB or more (plan_matvec never sends such rows) or the table cannot be had: the one
+// runtime outcome launch_matvec reports back to the plan, which then keeps the per-run prefix
 hipError_t launch_bs_tab(int k, int m, const dev::GfArgs& a, const uint8_t* const* rows, unsigned ns, uint64_t len,
                          hipStream_t st, bool* ok);
 hipError_t launch_bs16_repair_tab(int nd, int ne, const uint8_t* missing, const uint8_t* prow, const uint8_t* ainv,

@@ -86,8 +86,62 @@ hipError_t launch_flag_gather(uint32_t* tmp, uint32_t* out, const int* item, con
 constexpr int kLaunchMaxRows = 32;
 
 // Enqueue the product on `stream`.  Splits into as many launches as the kernel
-// argument block needs (inputs > 32, outputs > 32, or too many pointers).
+// argument block needs (inputs > 32, outputs > 32, or too many pointers): plan_matvec decides them,
+// launch_matvec fills one argument block per step and calls the launcher the step names.
 hipError_t launch_matvec(const MatVecJob& job, hipStream_t stream);
+
+// Which kernels run a job, decided in one place (gf_kernels.hip, whose header lists the families).
+// A pure host function: no HIP calls; it reads the job's scalar fields, coef, lens, the pointer
+// arrays (stride, alignment, span) and the A/B switches CFSEC_LUT, CFSEC_BS16, CFSEC_BS_TAB and
+// CFSEC_BS_CRC.  It returns the error launch_matvec returns for the job, or visits its launches in
+// order.  One step: rows [r0, r0 + mc) x inputs [c0, c0 + kc) of stripes [s0, s0 + ns), bytes
+// [off, off + prefix) of each by the bit-sliced 16 + 20 kernel `bs` names, then `tail` bytes by the
+// family kernel (either may be 0, not both).
+enum class MatVecFamily : int { kRuntimeK = 0, kFixedK, kDyadic, kDyadic16, kLookup, kBsPlain };
+enum class BsPrefix : int {
+  kNone = 0,
+  kEncode,  // launch_bs on the run (affine, or the run's stripes in the argument block)
+  kVerify,  // the bit-sliced repair with nothing missing, every row compared (affine runs)
+  kTable,   // launch_bs_tab: every stripe of a scattered job at once (s0 = 0, ns = nstripes, no tail);
+            // the runs that follow carry off = prefix and only the rows' tails
+};
+struct MatVecStep {
+  int r0, mc, c0, kc, s0, ns;
+  MatVecMode mode;  // resolved: kStoreVerify with nstore 0 / m folded, kAccum for c0 > 0
+  MatVecFamily family;
+  BsPrefix bs;
+  int M, OS, threads;          // runtime-k: rows per wave, waves per column chunk, workgroup size
+  int B, E;                    // dyadic: block size, trailing plain rows
+  uint64_t off, prefix, tail;  // off + prefix + tail = the run's (longest) length
+  int64_t sstride;             // != 0: an affine run (one pointer set, any stripe count)
+  uint32_t tile;               // bytes per workgroup of the family kernel
+  uint32_t grid_x, grid_y;     // of the family launch (0 when tail == 0)
+  const uint8_t* const* rows;  // kTable: every stripe's k inputs then m outputs (valid during the visit)
+  // kTable only, set by the visitor: false when the device row-offset table could not be had -- the
+  // one outcome the plan cannot know.  The plan then goes on as if it had not chosen the table.
+  bool table_ok;
+};
+using MatVecVisitor = hipError_t (*)(MatVecStep& step, void* ctx);  // != hipSuccess ends the plan
+hipError_t plan_matvec(const MatVecJob& job, MatVecVisitor visit, void* ctx);
+const char* matvec_family_name(MatVecFamily f);  // "runtime-k", "fixed-k", "dyadic", "dyadic-16", "lookup", "bs-plain"
+const char* bs_prefix_name(BsPrefix p);          // "none", "encode", "verify", "table"
+// CFSEC_TRACE_MATVEC (read per call) prints one stderr line per step launch_matvec dispatches:
+// "cfsec: matvec family=<name> bs=<none|encode|verify|table> mode=.. k=.. m=.. r0=.. c0=.. stripes=..
+// prefix=.. tail=.. affine=..".
+
+// launch_dy16_repair's decisions, the same way: per job the table launch, per run the affine
+// bit-sliced prefix, whether the checksums ride in that pass, and the dyadic tail.
+enum class RepairBs : int { kNone = 0, kAffine, kTable };
+struct RepairStep {
+  int s0, ns;
+  RepairBs bs;  // kTable: every stripe at once (s0 = 0), the runs after it carry off = prefix
+  int crc_rows;  // > 0: that many stored rows' checksums ride in this step's bit-sliced pass (whole rows)
+  uint64_t off, prefix, tail;
+  int64_t sstride;
+  const uint8_t* const* rows;  // kTable: as MatVecStep::rows (this table launch has no runtime fallback)
+};
+using RepairVisitor = hipError_t (*)(RepairStep& step, void* ctx);
+hipError_t plan_dy16_repair(const Dy16RepairJob& job, RepairVisitor visit, void* ctx);
 
 // crc32.ChecksumIEEE of n device shards of `len` bytes into device out[n].
 // Leaves the raw (pre-conditioning) word per shard in out; crc32_finalize turns it

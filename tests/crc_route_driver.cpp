@@ -4,6 +4,7 @@
 // library's routing predicates; nothing is launched and no shard memory is allocated.
 //
 //   crc_route_driver rs:N:M ... lrc:N:M:L:AZ:PUTQUORUM ...
+//   crc_route_driver matvec rs:N:M ... lrc:... gen:K:M ...     (the plans of launch_matvec, below)
 //
 // Output, one record per line:
 //   L <len> <nst0> <nst1> <nst2>                       the lengths and the stripe counts of each
@@ -18,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <random>
+#include <set>
 #include <string>
 #include <vector>
 
@@ -82,6 +84,109 @@ std::string cells(int k, int m, const uint8_t* coef, int stride, const std::vect
   return s;
 }
 
+// ---- "matvec" as the first argument: the plans of launch_matvec (plan_matvec) instead of the
+// checksum routes, for tests/test_matvec_route.py.  Records:
+//   mat <id> <tag> <k> <m> <coef hex>       tag: enc, rec, rep, fused, gen
+//   mv <id> <mode> <nstore> <len> <layout> <nstripes> <error> <steps>
+// <steps>: ';'-joined "family,bs,mode,r0,mc,c0,kc,s0,ns,off,prefix,tail,affine,M,OS,threads,B,E,tile,gx,gy"
+// ('-' when there are none).  Row addresses are synthesised and never dereferenced.
+bool g_matvec = false;
+std::set<std::string> g_seen;
+int g_next_id = 0;
+
+const uint64_t kMvLens[] = {1,    15,   16,   17,   2047, 2048, 2049, 4096, 4097, 0xFFFFFFFFull - 4096, 0xFFFFFFFFull - 4095,
+                            (512ull << 20) + 1};
+// (cap1x: cap1 with a visitor that reports every table launch as failed: the dispatcher's one fallback)
+const char* const kLayouts[] = {"one", "aff", "aff1", "cap", "cap1", "cap1x", "far", "lens33", "lens2p32"};
+struct StepLog {
+  std::string out;
+  bool refuse_table;
+};
+
+hipError_t print_step(MatVecStep& s, void* ctx) {
+  StepLog& log = *static_cast<StepLog*>(ctx);
+  std::string& out = log.out;
+  if (s.bs == BsPrefix::kTable && log.refuse_table) s.table_ok = false;
+  char b[256];
+  std::snprintf(b, sizeof b, "%s%s,%s,%d,%d,%d,%d,%d,%d,%d,%llu,%llu,%llu,%d,%d,%d,%d,%d,%d,%u,%u,%u", out.empty() ? "" : ";",
+                matvec_family_name(s.family), bs_prefix_name(s.bs), (int)s.mode, s.r0, s.mc, s.c0, s.kc, s.s0, s.ns,
+                (unsigned long long)s.off, (unsigned long long)s.prefix, (unsigned long long)s.tail, s.sstride != 0, s.M,
+                s.OS, s.threads, s.B, s.E, s.tile, s.grid_x, s.grid_y);
+  out += b;
+  return hipSuccess;
+}
+
+void mv_plan(int id, int k, int m, const uint8_t* coef, MatVecMode mode, int nstore, uint64_t len, const char* layout) {
+  const std::string lay = layout;
+  const int cap = 288 / (std::min(k, 32) + std::min(m, 32));  // stripes one argument block holds
+  const int nst = lay == "one" ? 1 : lay == "aff" || lay == "aff1" ? 2 : lay == "cap" ? cap : lay[0] == 'l' ? 33 : cap + 1;
+  const uint64_t base = 0x100000000000ull, pitch = (len + 255) / 256 * 256 + 256;
+  std::vector<const uint8_t*> in((size_t)nst * k);
+  std::vector<uint8_t*> out((size_t)nst * m);
+  for (int s = 0; s < nst; ++s)
+    for (int i = 0; i < k + m; ++i) {
+      uint64_t a = base + ((uint64_t)s * (k + m) + i) * pitch;
+      if (lay == "aff1" && i == 1) a += 1;                                 // one row 1 byte off, still affine
+      if (lay != "one" && lay != "aff" && lay != "aff1") a += 256ull * s * s;  // no common stride
+      if (lay == "far" && s == nst - 1) a += 8ull << 30;                   // the rows span >= 4 GiB
+      if (i < k) in[(size_t)s * k + i] = reinterpret_cast<const uint8_t*>(a);
+      else out[(size_t)s * m + i - k] = reinterpret_cast<uint8_t*>(a);
+    }
+  std::vector<uint64_t> lens;
+  if (lay[0] == 'l') {
+    for (int s = 0; s < nst; ++s) lens.push_back(s % 3 == 0 ? len : len / 2 + (uint64_t)(s & 1));
+    if (lay == "lens2p32") lens[5] = 1ull << 32;
+  }
+  MatVecJob job;
+  job.k = k;
+  job.m = m;
+  job.coef = coef;
+  job.len = lens.empty() ? (size_t)len : 0;
+  job.lens = lens.empty() ? nullptr : lens.data();
+  job.nstripes = nst;
+  job.in = in.data();
+  job.out = out.data();
+  job.mode = mode;
+  job.nstore = nstore;
+  job.flags = reinterpret_cast<uint32_t*>(base - 4096);
+  StepLog log{"", lay == "cap1x"};
+  const hipError_t e = plan_matvec(job, print_step, &log);
+  const std::string& steps = log.out;
+  std::printf("mv %d %d %d %llu %s %d %d %s\n", id, (int)mode, nstore, (unsigned long long)len, layout, nst, (int)e,
+              steps.empty() ? "-" : steps.c_str());
+}
+
+// every mode x length x layout for the named matrices; for the (thousands of) reconstruct matrices
+// two lengths, two modes and one layout, and for every 64th of them ("rep") every mode and layout at
+// three lengths
+void mv_matrix(const char* tag, int k, int m, const uint8_t* coef) {
+  if (m == 0) return;
+  const bool full = std::strcmp(tag, "rec") != 0;  // (reconstruct matrices repeat rarely: not looked up)
+  if (full && !g_seen.insert(std::to_string(k) + ":" + std::to_string(m) + ":" + hex(coef, (size_t)k * m)).second) return;
+  const int id = g_next_id++;
+  const bool rep = !full && id % 64 == 0;
+  std::printf("mat %d %s %d %d %s\n", id, rep ? "rep" : tag, k, m, hex(coef, (size_t)k * m).c_str());
+  const struct { MatVecMode mode; int nstore; } modes[] = {{MatVecMode::kStore, 0}, {MatVecMode::kStoreVerify, 1},
+                                                          {MatVecMode::kVerify, 0}, {MatVecMode::kStoreVerify, 0},
+                                                          {MatVecMode::kStoreVerify, m}};
+  for (int mi = 0; mi < (full || rep ? 5 : 2); ++mi)
+    for (uint64_t len : kMvLens) {
+      if (!full && len != 2049 && len != 4097 && !(rep && len == 17)) continue;
+      for (const char* lay : kLayouts) {
+        if (!full && !rep && std::strcmp(lay, "aff") != 0) continue;
+        if (!std::strcmp(lay, "lens2p32") && len != 4097) continue;
+        mv_plan(id, k, m, coef, modes[mi].mode, modes[mi].nstore, len, lay);
+      }
+    }
+}
+
+int generic(int k, int m) {
+  std::vector<uint8_t> coef((size_t)k * m);
+  for (size_t i = 0; i < coef.size(); ++i) coef[i] = (uint8_t)(1 + (i * 37 + 11) % 255);
+  mv_matrix("gen", k, m, coef.data());
+  return 0;
+}
+
 int rs_shape(int N, int M) {
   std::unique_ptr<RSEngine> e;
   if (RSEngine::create(N, M, -1, &e) != CFSEC_OK) return 1;
@@ -135,6 +240,10 @@ int rs_shape(int N, int M) {
       const uint8_t* coef = plan.rows.v.data();
       static const uint8_t none = 0;
       if (m == 0) coef = &none;  // (an empty matrix: nothing to rebuild)
+      if (g_matvec) {
+        mv_matrix(!data_only && (int)s.size() == M && s[0] == N ? "enc" : "rec", N, m, coef);
+        continue;
+      }
       std::string out = cells(N, m, coef, T, slot);
       for (int c2 = 0; c2 < N; ++c2) slot[c2] = plan.valid[c2];
       out += cells(N, m, coef, T, slot);
@@ -162,6 +271,10 @@ int lrc_mode(int N, int M, int L, int AZ, int PQ) {
   if (enc->repair_rows(nullptr, 0, want.data(), M + L, in.data(), rows.data()) != CFSEC_OK) return 2;
   for (int i = 0; i < N; ++i)
     if (in[i] != i) return 3;
+  if (g_matvec) {
+    mv_matrix("fused", N, M + L, rows.data());
+    return 0;
+  }
   std::vector<int> slot(N + M + L);
   for (int i = 0; i < N + M + L; ++i) slot[i] = i;
   std::string plain;
@@ -177,15 +290,17 @@ int lrc_mode(int N, int M, int L, int AZ, int PQ) {
 }  // namespace
 
 int main(int argc, char** argv) {
-  for (int li = 0; li < kNLens; ++li)
+  g_matvec = argc > 1 && !std::strcmp(argv[1], "matvec");
+  for (int li = 0; li < kNLens && !g_matvec; ++li)
     std::printf("L %llu %d %d %d\n", (unsigned long long)kLens[li], stripes(kLens[li], 0), stripes(kLens[li], 1),
                 stripes(kLens[li], 2));
-  for (int i = 1; i < argc; ++i) {
+  for (int i = g_matvec ? 2 : 1; i < argc; ++i) {
     int a[5] = {0, 0, 0, 0, 0};
     int rc = 64;
     if (std::sscanf(argv[i], "rs:%d:%d", &a[0], &a[1]) == 2) rc = rs_shape(a[0], a[1]);
     else if (std::sscanf(argv[i], "lrc:%d:%d:%d:%d:%d", &a[0], &a[1], &a[2], &a[3], &a[4]) == 5)
       rc = lrc_mode(a[0], a[1], a[2], a[3], a[4]);
+    else if (g_matvec && std::sscanf(argv[i], "gen:%d:%d", &a[0], &a[1]) == 2) rc = generic(a[0], a[1]);
     if (rc != 0) {
       std::fprintf(stderr, "crc_route_driver: %s failed (%d)\n", argv[i], rc);
       return 1;
