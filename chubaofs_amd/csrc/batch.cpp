@@ -20,10 +20,7 @@
 namespace cfsec {
 namespace {
 
-constexpr size_t kSlot = 256;                      // staging rows start on 256-B boundaries
 constexpr size_t kLaneBudget = size_t(256) << 20;  // staging bytes per lane of a pageable batch
-
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // The HIP device that owns device memory p, or -1.
 int device_of(const void* p) {
@@ -36,25 +33,52 @@ int device_of(const void* p) {
   return attr.device;
 }
 
-// KRS/reedsolomon.go:1314-1339 checkShards / shardSize (as engine.cpp's).
-Status stripe_size(const cfsec_shard* shards, int n, bool nilok, size_t* size) {
-  size_t s = 0;
-  for (int i = 0; i < n; ++i)
-    if (shards[i].len != 0) {
-      s = shards[i].len;
-      break;
-    }
-  if (s == 0) return CFSEC_ERR_SHARD_NO_DATA;
-  for (int i = 0; i < n; ++i)
-    if (shards[i].len != s && (shards[i].len != 0 || !nilok)) return CFSEC_ERR_SHARD_SIZE;
-  *size = s;
-  return CFSEC_OK;
+// A whole stripe an Encode or a Verify takes: every shard of one size (checkShards), every one there.
+Status whole_stripe_ok(const cfsec_shard* sh, int n, size_t* size) {
+  Status st = check_shards(sh, n, false, size);
+  for (int i = 0; i < n && st == CFSEC_OK; ++i)
+    if (!sh[i].data) st = CFSEC_ERR_INVALID_ARG;
+  return st;
+}
+
+// The tasks planned over the stripes a call kept (owner = index among those) belong to the items
+// pos[owner] of the call: the item's verify word, its device, and -- with crc -- the checksums of its
+// rebuilt shards (blobnode ShardCrc32) at words [item * n, item * n + n).
+void stamp_items(std::vector<StripeTask>& tasks, const std::vector<int>& pos, const CrcOut* crc, int n) {
+  for (auto& t : tasks) {
+    t.owner = pos[t.owner];
+    t.crc = crc ? 1 : 0;
+    t.crc_word = (int64_t)t.owner * n;
+  }
+}
+
+// A set of tasks with resolved device addresses, launched on one stream: the in-place tasks of a
+// phase, or one staged chunk.  rows[i][p] = task i's row p of plan->in followed by plan->out.
+struct Part {
+  std::vector<StripeTask*> tasks;
+  std::vector<uint8_t* const*> rows;
+};
+
+// The rows a task checksums: f(position in plan->in followed by plan->out, CrcOut word) for every
+// input row (crc == 2) and every stored row whose word lies in [0, nwords).
+template <class F>
+void for_each_crc_row(const StripeTask& t, size_t nwords, F f) {
+  if (!t.crc) return;
+  const size_t k = t.plan->in.size();
+  const auto visit = [&](size_t p, int row) {
+    const int64_t w = t.crc_word + (t.crc_map ? t.crc_map[row] : row);
+    if (w >= 0 && (size_t)w < nwords) f(p, (size_t)w);
+  };
+  if (t.crc == 2)
+    for (size_t c = 0; c < k; ++c) visit(c, t.plan->in[c]);
+  for (int r = 0; r < t.plan->nstore; ++r) visit(k + r, t.plan->out[r]);
 }
 
 // Rows of one device launch group: stripes sharing a plan.
 struct Group {
   const StripePlan* plan = nullptr;
   std::vector<StripeTask*> tasks;
+  std::vector<size_t> at;          // tasks[i] is task at[i] of the part
   std::vector<const uint8_t*> in;  // [tasks * k]
   std::vector<uint8_t*> out;       // [tasks * m]
   std::vector<uint64_t> lens;
@@ -72,62 +96,15 @@ struct Group {
   std::vector<char>* crc_done = nullptr;
 };
 
-hipError_t launch_group_run(const Group& g, size_t t0, size_t t1, uint32_t* dflags, hipStream_t s);
-
-// Enqueue one group: maximal runs of stripes that sit at one stride from each other (every row)
-// launch as affine batches of any size; the rest as pointer tables.
-hipError_t launch_group(const Group& g, uint32_t* dflags, hipStream_t s) {
-  const size_t k = g.plan->in.size(), m = g.plan->out.size(), nt = g.tasks.size();
-  bool uniform = true;
-  for (uint64_t l : g.lens) uniform = uniform && l == g.lens[0];
-  if (!uniform || nt < 3) return launch_group_run(g, 0, nt, dflags, s);
-  const auto addr = [](const void* p) { return (int64_t)(uintptr_t)p; };
-  const auto stride_ok = [&](size_t t, int64_t d) {  // stripe t+1 = stripe t + d on every row
-    for (size_t c = 0; c < k; ++c)
-      if (addr(g.in[(t + 1) * k + c]) - addr(g.in[t * k + c]) != d) return false;
-    for (size_t r = 0; r < m; ++r)
-      if (addr(g.out[(t + 1) * m + r]) - addr(g.out[t * m + r]) != d) return false;
-    if (g.plan->dy16) {
-      const size_t mo = g.plan->dy16->rows.size();
-      for (size_t r = 0; r < mo; ++r)
-        if (addr(g.hout[(t + 1) * mo + r]) - addr(g.hout[t * mo + r]) != d) return false;
-    }
-    return true;
-  };
-  // Runs shorter than kMinRun stripes (separately allocated shards: blobnode's per-vuid buffers)
-  // are not launched one by one -- a launch per stripe leaves most of the GPU idle (C5's tasklet
-  // with every shard at its own address: 64 launches of 16 workgroups, 1.9 ms) -- but gathered into
-  // pointer-table runs, which the launchers split into as many stripes per launch as their argument
-  // block holds.
-  constexpr size_t kMinRun = 4;
-  const auto run_end = [&](size_t t0) {
-    size_t t1 = t0 + 1;
-    if (t1 < nt) {
-      const int64_t d = addr(g.in[t1 * k]) - addr(g.in[t0 * k]);
-      while (t1 < nt && d != 0 && stride_ok(t1 - 1, d)) ++t1;
-    }
-    return t1;
-  };
-  size_t t0 = 0;
-  while (t0 < nt) {
-    size_t t1 = run_end(t0);
-    if (t1 - t0 < kMinRun) {  // extend over the following short runs
-      while (t1 < nt) {
-        const size_t t2 = run_end(t1);
-        if (t2 - t1 >= kMinRun) break;
-        t1 = t2;
-      }
-    }
-    const hipError_t e = launch_group_run(g, t0, t1, dflags, s);
-    if (e != hipSuccess) return e;
-    t0 = t1;
-  }
-  return hipSuccess;
-}
-
 // Stripes [t0, t1) of a group: the mixed store/compare product, split into a store and a compare
 // launch when the rows exceed one launch.
 hipError_t launch_group_run(const Group& g, size_t t0, size_t t1, uint32_t* dflags, hipStream_t s) {
+  // one length for the run: no per-stripe lengths, so stripes carved from one pitched buffer run
+  // as a single affine launch (any number of stripes) instead of 8-32 per launch
+  bool uniform = true;
+  for (size_t t = t0; t < t1; ++t) uniform = uniform && g.lens[t] == g.lens[t0];
+  const uint64_t* lens = uniform ? nullptr : g.lens.data() + t0;
+  uint32_t* flags = g.direct ? g.direct + t0 : dflags + g.flag0 + t0;
   if (const Dy16Plan* d = g.plan->dy16.get()) {
     Dy16RepairJob job;
     job.nd = d->nd;
@@ -144,11 +121,9 @@ hipError_t launch_group_run(const Group& g, size_t t0, size_t t1, uint32_t* dfla
     job.in = g.in.data() + t0 * 16;
     job.e = d->e;
     job.out = g.hout.data() + t0 * d->rows.size();
-    bool uniform = true;
-    for (size_t t = t0; t < t1; ++t) uniform = uniform && g.lens[t] == g.lens[t0];
-    job.lens = uniform ? nullptr : g.lens.data() + t0;
+    job.lens = lens;
     job.len = g.lens[t0];
-    job.flags = g.direct ? g.direct + t0 : dflags + g.flag0 + t0;
+    job.flags = flags;
     if (t0 == 0) {
       job.zero_words = g.zero_words;
       job.nzero = g.nzero;
@@ -162,20 +137,11 @@ hipError_t launch_group_run(const Group& g, size_t t0, size_t t1, uint32_t* dfla
     }
     return launch_dy16_repair(job, s);
   }
-  MatVecJob job;
-  job.k = (int)g.plan->in.size();
-  job.m = (int)g.plan->out.size();
-  job.coef = g.plan->rows.v.data();
-  job.nstripes = (int)(t1 - t0);
-  job.in = g.in.data() + t0 * job.k;
-  job.out = g.out.data() + t0 * job.m;
-  // one length for the run: no per-stripe lengths, so stripes carved from one pitched buffer run
-  // as a single affine launch (any number of stripes) instead of 8-32 per launch
-  bool uniform = true;
-  for (size_t t = t0; t < t1; ++t) uniform = uniform && g.lens[t] == g.lens[t0];
-  job.lens = uniform ? nullptr : g.lens.data() + t0;
-  job.len = g.lens[t0];
-  job.flags = g.direct ? g.direct + t0 : dflags + g.flag0 + t0;
+  const size_t nin = g.plan->in.size(), nout = g.plan->out.size();
+  MatVecJob job = matvec_job((int)nin, (int)nout, g.plan->rows.v.data(), g.lens[t0], (int)(t1 - t0),
+                             g.in.data() + t0 * nin, g.out.data() + t0 * nout);
+  job.lens = lens;
+  job.flags = flags;
   job.mode = MatVecMode::kStoreVerify;
   job.nstore = g.plan->nstore;
   if (job.m <= kLaunchMaxRows || job.nstore == 0 || job.nstore == job.m) return launch_matvec(job, s);
@@ -196,6 +162,38 @@ hipError_t launch_group_run(const Group& g, size_t t0, size_t t1, uint32_t* dfla
   b.mode = MatVecMode::kVerify;
   hipError_t e = launch_matvec(a, s);
   return e != hipSuccess ? e : launch_matvec(b, s);
+}
+
+// Enqueue one group: maximal runs of stripes that sit at one stride from each other (every row)
+// launch as affine batches of any size; the rest as pointer tables.
+hipError_t launch_group(const Group& g, uint32_t* dflags, hipStream_t s) {
+  const size_t mo = g.plan->dy16 ? g.plan->dy16->rows.size() : 0;
+  for (const auto& run : split_runs(g.in.data(), g.plan->in.size(), g.out.data(), g.plan->out.size(), g.hout.data(), mo,
+                                    g.lens.data(), g.tasks.size())) {
+    const hipError_t e = launch_group_run(g, run.first, run.second, dflags, s);
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
+// The stride of a group's checksum words, for the launches that checksum in the product's own pass:
+// every task checksums in `mode` and is the only checksummed task of its item (no other task writes
+// that item's words), no index remap, one length, task i's words at word(task 0) + i * stride with
+// the stride past maxrow (the largest shard index checksummed), all of them within [0, nwords).
+// 0 when the group is not laid out so.
+int64_t crc_word_stride(const Group& g, int mode, int maxrow, size_t nwords,
+                        const std::map<int, int>& tasks_per_owner) {
+  const size_t nt = g.tasks.size();
+  const int64_t w0 = g.tasks[0]->crc_word;
+  int64_t cs = maxrow + 1;  // a single task: any stride that clears its rows
+  for (size_t i = 0; i < nt; ++i) {
+    const StripeTask* t = g.tasks[i];
+    if (t->crc != mode || t->crc_map || g.lens[i] != g.lens[0] || tasks_per_owner.at(t->owner) != 1) return 0;
+    if (i == 1) cs = t->crc_word - w0;
+    if (i >= 1 && t->crc_word - g.tasks[i - 1]->crc_word != cs) return 0;
+  }
+  if (cs <= maxrow || w0 < 0 || (size_t)(w0 + cs * (int64_t)nt) > nwords) return 0;
+  return cs;
 }
 
 // A group whose product is a plain store the fused product + CRC kernels have a route for
@@ -220,31 +218,16 @@ bool fused_crc_group(const Group& g, uint32_t* dcrc, size_t nwords, const std::m
   if (len == 0) return false;
   const StripeTask* t0 = g.tasks[0];
   const int mode = t0->crc;  // 2: inputs and outputs, 1: the stored outputs only
-  if (mode == 0) return false;
-  int64_t cs = 0;
-  for (size_t i = 0; i < nt; ++i) {
-    const StripeTask* t = g.tasks[i];
-    if (t->crc != mode || t->crc_map || g.lens[i] != len || tasks_per_owner.at(t->owner) != 1) return false;
-    if (i == 1) cs = t->crc_word - t0->crc_word;
-    if (i >= 1 && t->crc_word - g.tasks[i - 1]->crc_word != cs) return false;
-  }
+  if (mode == 0) return false;  // mode rule: any checksum mode, the one the tasks share
   int maxrow = 0;
   for (int c : p.in) maxrow = std::max(maxrow, c);
   for (int o : p.out) maxrow = std::max(maxrow, o);
-  if (nt == 1) cs = maxrow + 1;
-  if (cs <= maxrow || cs > 256 || t0->crc_word < 0 || (size_t)(t0->crc_word + cs * (int64_t)nt) > nwords) return false;
+  const int64_t cs = crc_word_stride(g, mode, maxrow, nwords, tasks_per_owner);
+  if (cs == 0 || cs > 256) return false;  // no fused route takes a stride past 256 words (kernels.hpp)
   std::vector<int> slot(k + m);
   for (int c = 0; c < k; ++c) slot[c] = mode == 2 ? p.in[c] : -1;
   for (int r = 0; r < m; ++r) slot[k + r] = p.out[r];
-  MatVecJob job;
-  job.k = k;
-  job.m = m;
-  job.coef = p.rows.v.data();
-  job.len = len;
-  job.nstripes = (int)nt;
-  job.in = g.in.data();
-  job.out = g.out.data();
-  job.mode = MatVecMode::kStore;
+  const MatVecJob job = matvec_job(k, m, p.rows.v.data(), len, (int)nt, g.in.data(), g.out.data());
   // the route of exactly this job (its slots, length and stripe count): a shape only the bit-sliced
   // kernel covers has one with every shard checksummed (mode 2) and the tile counts in range only
   if (!matvec_crc_accepts(job, (int)cs, slot.data())) return false;
@@ -288,18 +271,12 @@ bool dy16_crc_group(Group& g, uint32_t* dcrc, size_t nwords, const std::map<int,
   std::sort(stored.begin(), stored.end());
   std::sort(sorted_rows.begin(), sorted_rows.end());
   if (stored != sorted_rows) return false;  // the separate pass would checksum other rows
-  int64_t cs = 0;
-  for (size_t i = 0; i < nt; ++i) {
-    const StripeTask* t = g.tasks[i];
-    if (t->crc != 1 || t->crc_map || g.lens[i] != len || tasks_per_owner.at(t->owner) != 1) return false;
-    if (i == 1) cs = t->crc_word - g.tasks[0]->crc_word;
-    if (i >= 1 && t->crc_word - g.tasks[i - 1]->crc_word != cs) return false;
-  }
   const int maxrow = *std::max_element(rows.begin(), rows.end());
-  if (nt == 1) cs = maxrow + 1;
-  const int64_t w0 = g.tasks[0]->crc_word;
-  if (cs <= maxrow || maxrow > 255 || w0 < 0 || (size_t)(w0 + cs * (int64_t)nt) > nwords) return false;
-  g.crc_words = dcrc + w0;
+  if (maxrow > 255) return false;  // crc_slot holds bytes; the stride itself is not bounded here
+  // mode rule: the stored rows only (crc == 1), what a repair checksums
+  const int64_t cs = crc_word_stride(g, 1, maxrow, nwords, tasks_per_owner);
+  if (cs == 0) return false;
+  g.crc_words = dcrc + g.tasks[0]->crc_word;
   g.crc_stride = (uint32_t)cs;
   for (size_t k = 0; k < rows.size(); ++k) g.crc_slot[k] = (uint8_t)rows[k];
   done->assign(nt, 0);
@@ -308,12 +285,12 @@ bool dy16_crc_group(Group& g, uint32_t* dcrc, size_t nwords, const std::map<int,
 }
 
 // Group tasks by plan (first appearance order) and give each group consecutive flag words from
-// *next_flag; row pointers from ptr(task, shard index).
-template <class Ptr>
-std::vector<Group> make_groups(const std::vector<StripeTask*>& tasks, int* next_flag, Ptr ptr) {
+// *next_flag; row pointers from the part's resolved addresses.
+std::vector<Group> make_groups(const Part& part, int* next_flag) {
   std::vector<Group> groups;
   std::map<const StripePlan*, size_t> index;
-  for (StripeTask* t : tasks) {
+  for (size_t i = 0; i < part.tasks.size(); ++i) {
+    StripeTask* t = part.tasks[i];
     auto it = index.find(t->plan);
     if (it == index.end()) {
       it = index.emplace(t->plan, groups.size()).first;
@@ -321,28 +298,32 @@ std::vector<Group> make_groups(const std::vector<StripeTask*>& tasks, int* next_
       groups.back().plan = t->plan;
     }
     groups[it->second].tasks.push_back(t);
+    groups[it->second].at.push_back(i);
   }
   for (Group& g : groups) {
+    const std::vector<int>&in = g.plan->in, &out = g.plan->out;
+    const size_t k = in.size(), m = out.size();
     g.flag0 = *next_flag;
-    g.in.reserve(g.tasks.size() * g.plan->in.size());
-    g.out.reserve(g.tasks.size() * g.plan->out.size());
+    g.in.reserve(g.tasks.size() * k);
+    g.out.reserve(g.tasks.size() * m);
     g.lens.reserve(g.tasks.size());
-    // dy16 output rows: rows the kernel neither stores nor compares (inputs; parity not verified)
-    // get any pointer the task has -- decided once per plan, not per task
-    std::vector<int> hrow;
+    // dy16 output rows, as positions in the task's rows: rows the kernel neither stores nor compares
+    // (inputs; parity not verified) get any pointer the task has (its first input's) -- decided once
+    // per plan, not per task
+    std::vector<size_t> hrow;
     if (g.plan->dy16)
       for (int idx : g.plan->dy16->rows) {
-        const bool known = std::find(g.plan->in.begin(), g.plan->in.end(), idx) != g.plan->in.end() ||
-                           std::find(g.plan->out.begin(), g.plan->out.end(), idx) != g.plan->out.end();
-        hrow.push_back(known ? idx : g.plan->in[0]);
+        const size_t c = std::find(in.begin(), in.end(), idx) - in.begin();
+        const size_t o = std::find(out.begin(), out.end(), idx) - out.begin();
+        hrow.push_back(c < k ? c : o < m ? k + o : 0);
       }
     g.hout.reserve(g.tasks.size() * hrow.size());
-    for (size_t i = 0; i < g.tasks.size(); ++i) {
-      StripeTask* t = g.tasks[i];
-      for (int c : g.plan->in) g.in.push_back(ptr(t, c));
-      for (int o : g.plan->out) g.out.push_back(const_cast<uint8_t*>(ptr(t, o)));
-      g.lens.push_back(t->len);
-      for (int idx : hrow) g.hout.push_back(const_cast<uint8_t*>(ptr(t, idx)));
+    for (size_t i : g.at) {
+      uint8_t* const* rows = part.rows[i];
+      g.in.insert(g.in.end(), rows, rows + k);
+      g.out.insert(g.out.end(), rows + k, rows + k + m);
+      g.lens.push_back(part.tasks[i]->len);
+      for (size_t p : hrow) g.hout.push_back(rows[p]);
     }
     *next_flag += (int)g.tasks.size();
   }
@@ -350,6 +331,69 @@ std::vector<Group> make_groups(const std::vector<StripeTask*>& tasks, int* next_
 }
 
 }  // namespace
+
+std::vector<std::pair<size_t, size_t>> split_runs(const uint8_t* const* in, size_t k, const uint8_t* const* out,
+                                                  size_t m, const uint8_t* const* hout, size_t mo,
+                                                  const uint64_t* lens, size_t nt) {
+  std::vector<std::pair<size_t, size_t>> runs;
+  bool uniform = true;
+  for (size_t t = 0; t < nt; ++t) uniform = uniform && lens[t] == lens[0];
+  if (!uniform || nt < 3) {
+    runs.emplace_back(0, nt);
+    return runs;
+  }
+  const auto addr = [](const void* p) { return (int64_t)(uintptr_t)p; };
+  const auto stride_ok = [&](size_t t, int64_t d) {  // stripe t+1 = stripe t + d on every row
+    for (size_t c = 0; c < k; ++c)
+      if (addr(in[(t + 1) * k + c]) - addr(in[t * k + c]) != d) return false;
+    for (size_t r = 0; r < m; ++r)
+      if (addr(out[(t + 1) * m + r]) - addr(out[t * m + r]) != d) return false;
+    for (size_t r = 0; r < mo; ++r)
+      if (addr(hout[(t + 1) * mo + r]) - addr(hout[t * mo + r]) != d) return false;
+    return true;
+  };
+  // Runs shorter than kMinRun stripes (separately allocated shards: blobnode's per-vuid buffers)
+  // are not launched one by one -- a launch per stripe leaves most of the GPU idle (C5's tasklet
+  // with every shard at its own address: 64 launches of 16 workgroups, 1.9 ms) -- but gathered into
+  // pointer-table runs, which the launchers split into as many stripes per launch as their argument
+  // block holds.
+  constexpr size_t kMinRun = 4;
+  const auto run_end = [&](size_t t0) {
+    size_t t1 = t0 + 1;
+    if (t1 < nt) {
+      const int64_t d = addr(in[t1 * k]) - addr(in[t0 * k]);
+      while (t1 < nt && d != 0 && stride_ok(t1 - 1, d)) ++t1;
+    }
+    return t1;
+  };
+  size_t t0 = 0;
+  while (t0 < nt) {
+    size_t t1 = run_end(t0);
+    if (t1 - t0 < kMinRun) {  // extend over the following short runs
+      while (t1 < nt) {
+        const size_t t2 = run_end(t1);
+        if (t2 - t1 >= kMinRun) break;
+        t1 = t2;
+      }
+    }
+    runs.emplace_back(t0, t1);
+    t0 = t1;
+  }
+  return runs;
+}
+
+size_t pack_chunk(const StripeTask* const* tasks, size_t n, size_t i0, size_t lane_bytes,
+                  std::vector<size_t>* offsets) {
+  offsets->clear();
+  size_t used = 0, i1 = i0;
+  for (; i1 < n; ++i1) {
+    const size_t sl = align_up(tasks[i1]->len, kSlotAlign);
+    const size_t nrows = tasks[i1]->plan->in.size() + tasks[i1]->plan->out.size();
+    if (i1 > i0 && used + sl * nrows > lane_bytes) break;
+    for (size_t p = 0; p < nrows; ++p, used += sl) offsets->push_back(used);
+  }
+  return i1;
+}
 
 void partition_stripes(const uint64_t* bytes, int n, int ndev, int* dev) {
   // Stripe i goes to the device whose share of the byte total holds the midpoint of stripe i's
@@ -513,27 +557,29 @@ void RSEngine::plan_dy16(const std::vector<bool>& present, const Matrix& dec, St
   plan->dy16 = std::move(d);
 }
 
-Status RSEngine::encode_stripes(cfsec_shard* const* stripes, int nst, int mem, int* status) {
-  if (!stripes || !status || nst < 0) return CFSEC_ERR_INVALID_ARG;
+StripePlan whole_stripe_plan(int k, int total, const Matrix& rows, int nstore) {
   StripePlan plan;
-  for (int i = 0; i < k_; ++i) plan.in.push_back(i);
-  for (int i = k_; i < total(); ++i) plan.out.push_back(i);
-  plan.nstore = m_;
-  plan.rows = parity_;
+  for (int i = 0; i < k; ++i) plan.in.push_back(i);
+  for (int i = k; i < total; ++i) plan.out.push_back(i);
+  plan.nstore = nstore;
+  plan.rows = rows;
+  return plan;
+}
+
+Status RSEngine::whole_stripes(cfsec_shard* const* stripes, int nst, int mem, int* status, int nstore) {
+  if (!stripes || !status || nst < 0) return CFSEC_ERR_INVALID_ARG;
+  const StripePlan plan = whole_stripe_plan(k_, total(), parity_, nstore);
   std::vector<StripeTask> tasks;
   for (int s = 0; s < nst; ++s) {
-    status[s] = CFSEC_OK;
     size_t S = 0;
-    Status st = stripes[s] ? stripe_size(stripes[s], total(), false, &S) : CFSEC_ERR_INVALID_ARG;
-    for (int i = 0; i < total() && st == CFSEC_OK; ++i)
-      if (!stripes[s][i].data) st = CFSEC_ERR_INVALID_ARG;
-    if (st != CFSEC_OK) {
-      status[s] = st;
-      continue;
-    }
-    if (m_ > 0) tasks.push_back(StripeTask{stripes[s], &plan, S, &status[s], 0, 0, s});
+    status[s] = stripes[s] ? whole_stripe_ok(stripes[s], total(), &S) : CFSEC_ERR_INVALID_ARG;
+    if (status[s] == CFSEC_OK && m_ > 0) tasks.push_back(StripeTask{stripes[s], &plan, S, &status[s], 0, 0, s});
   }
   return run_stripes(tasks, mem);
+}
+
+Status RSEngine::encode_stripes(cfsec_shard* const* stripes, int nst, int mem, int* status) {
+  return whole_stripes(stripes, nst, mem, status, m_);
 }
 
 Status RSEngine::stripes_one_by_one(cfsec_shard* const* stripes, int nst, int mem, bool reconstruct, bool verify,
@@ -557,25 +603,7 @@ Status RSEngine::stripes_one_by_one(cfsec_shard* const* stripes, int nst, int me
 Status RSEngine::verify_stripes(cfsec_shard* const* stripes, int nst, int mem, int* status) {
   if (!stripes || !status || nst < 0) return CFSEC_ERR_INVALID_ARG;
   if (k_ > kLaunchMaxRows && m_ > 0) return stripes_one_by_one(stripes, nst, mem, false, true, status);
-  StripePlan plan;
-  for (int i = 0; i < k_; ++i) plan.in.push_back(i);
-  for (int i = k_; i < total(); ++i) plan.out.push_back(i);
-  plan.nstore = 0;
-  plan.rows = parity_;
-  std::vector<StripeTask> tasks;
-  for (int s = 0; s < nst; ++s) {
-    status[s] = CFSEC_OK;
-    size_t S = 0;
-    Status st = stripes[s] ? stripe_size(stripes[s], total(), false, &S) : CFSEC_ERR_INVALID_ARG;
-    for (int i = 0; i < total() && st == CFSEC_OK; ++i)
-      if (!stripes[s][i].data) st = CFSEC_ERR_INVALID_ARG;
-    if (st != CFSEC_OK) {
-      status[s] = st;
-      continue;
-    }
-    if (m_ > 0) tasks.push_back(StripeTask{stripes[s], &plan, S, &status[s], 0, 0, s});
-  }
-  return run_stripes(tasks, mem);
+  return whole_stripes(stripes, nst, mem, status, 0);
 }
 
 Status RSEngine::reconstruct_stripes(cfsec_shard* const* stripes, int nst, int mem, bool verify, int* status) {
@@ -600,7 +628,7 @@ void RSEngine::plan_reconstruct_tasks(cfsec_shard* const* stripes, int nst, bool
     status[s] = CFSEC_OK;
     cfsec_shard* sh = stripes[s];
     size_t S = 0;
-    Status st = sh ? stripe_size(sh, total(), true, &S) : CFSEC_ERR_INVALID_ARG;
+    Status st = sh ? check_shards(sh, total(), true, &S) : CFSEC_ERR_INVALID_ARG;
     if (st != CFSEC_OK) {
       status[s] = st;
       continue;
@@ -656,14 +684,7 @@ void RSEngine::plan_reconstruct_tasks(cfsec_shard* const* stripes, int nst, bool
         std::memcpy(cut.rows.v.data(), plan->rows.v.data(), (size_t)cut.nstore * k_);
         so = store->add(cut);
       }
-      if (!vplan) {
-        StripePlan v;
-        for (int i = 0; i < k_; ++i) v.in.push_back(i);
-        for (int i = k_; i < total(); ++i) v.out.push_back(i);
-        v.nstore = 0;
-        v.rows = parity_;
-        vplan = store->add(v);
-      }
+      if (!vplan) vplan = store->add(whole_stripe_plan(k_, total(), parity_, 0));
       use = so;
       StripeTask vt{sh, vplan, S, &status[s], 0, phase + 1, owner0 + s};
       tasks->push_back(vt);
@@ -693,8 +714,7 @@ const StripePlan* RSEngine::cached_plan(const std::vector<bool>& present, bool f
 }
 
 bool RSEngine::split_verify(const StripePlan& p) const {
-  const int checks = (int)p.out.size() - p.nstore;
-  if (checks <= 0 || p.nextra > 0) return false;
+  if (!p.compares() || p.nextra > 0) return false;
   static const int mode = [] {
     const char* e = getenv("CFSEC_VERIFY_SPLIT");
     return e ? atoi(e) : -1;
@@ -780,112 +800,115 @@ Status RSEngine::run_stripes(std::vector<StripeTask>& tasks, int mem, const Asyn
   return st[0];
 }
 
-Status RSEngine::run_device(std::vector<StripeTask*>& tasks, int mem, DeviceContext* ctx, const AsyncOut* async,
-                            const CrcOut* crc) {
-  HostTimer whole("  run_device");
-  std::unique_ptr<HostTimer> tm(new HostTimer("    classify + acquire"));
-  DeviceGuard g(ctx->device());
-  if (!g.ok()) return hip_status(hipErrorInvalidDevice, "hipSetDevice");
-  const int n = (int)tasks.size();
+namespace {
+
+// One run_device call: its workspace and lanes, what it found out about the tasks, and the flag and
+// checksum bookkeeping of the parts launched so far.
+struct BatchRun {
+  const AsyncOut* async;
+  const CrcOut* crc;
+  DeviceContext::Workspace* ws = nullptr;
+  // asynchronous calls run on the caller's stream (NULL: the legacy default stream); synchronous
+  // ones on the workspace's streams, ordered after the legacy default stream for device memory
+  hipStream_t lane[2] = {nullptr, nullptr};
+  int nlanes = 1;
+  size_t lane_bytes = 0, staged_total = 0;
   // which stripes the GPU addresses in place (device memory, or page-locked host memory on every
   // row the product touches) and which go through staging (pageable host memory)
-  std::vector<StripeTask*> direct, staged;
-  std::map<std::pair<const StripeTask*, int>, uint8_t*> alias;
+  Part direct;
+  std::vector<StripeTask*> staged;
+  std::vector<uint8_t*> addr;  // the rows of `direct`
   int nphase = 1, nitems = 0;
   bool checks = false;  // some task compares rows (Verify)
   bool sums = false;    // some task checksums rows
+  // checksum words: the caller's device array (asynchronous) or the workspace's, zeroed first (the
+  // CRC kernel XOR-accumulates)
+  uint32_t* dcrc = nullptr;
+  bool zero_first = false;             // the first in-place launch zeroes the words (begin)
+  std::map<int, int> tasks_per_owner;  // a bid with several checksummed tasks keeps the separate pass
+                                       // (EnableVerify's compare task writes no words: not counted)
+  uint32_t* fdirect = nullptr;  // the items' Verify words, where groups may write them directly (begin)
+  int next_flag = 0;
+  std::vector<std::pair<StripeTask*, int>> flags;  // (task, flag word; -1: written directly)
+  int chunk = 0;                                   // staged chunks so far: chunk c runs on lane c % nlanes
+
+  Status join(int from, int to) { return lane_wait(ws->ev, lane[from], lane[to]); }
+  void classify(const std::vector<StripeTask*>& tasks, int mem);
+  void size_lanes();
+  Status acquire(DeviceContext* ctx, size_t ntasks);
+  Status begin(DeviceContext* ctx, int mem, const std::vector<StripeTask*>& tasks);
+  Status run_phase(int ph);
+  Status run_staged(const std::vector<StripeTask*>& sph);
+  Status launch_part(const Part& part, hipStream_t s, bool fuse_crc);
+  Status checksum(const Part& part, const std::vector<char>& taken, hipStream_t s);
+  Status gather(Status st);
+  void hand_back(const std::vector<StripeTask*>& tasks);
+};
+
+// Sort the tasks into in-place and staged ones, resolving every row's device address once.
+void BatchRun::classify(const std::vector<StripeTask*>& tasks, int mem) {
+  size_t nrows = 0;
+  for (const StripeTask* t : tasks) nrows += t->plan->in.size() + t->plan->out.size();
+  addr.resize(nrows);
+  uint8_t** rows = addr.data();
   for (StripeTask* t : tasks) {
     sums = sums || (t->crc && crc && crc->words && crc->n);
     nphase = std::max(nphase, t->phase + 1);
     nitems = std::max(nitems, t->owner + 1);
-    checks = checks || t->plan->out.size() > (size_t)t->plan->nstore;
+    checks = checks || t->plan->compares();
+    if (t->crc) ++tasks_per_owner[t->owner];
+    const size_t k = t->plan->in.size(), n = k + t->plan->out.size();
     bool in_place = true;
-    if (mem == CFSEC_MEM_HOST) {
-      for (int c : t->plan->in) {
-        uint8_t* d = nullptr;
-        in_place = in_place && device_alias(t->shards[c].data, &d);
-        alias[{t, c}] = d;
-      }
-      for (int o : t->plan->out) {
-        uint8_t* d = nullptr;
-        in_place = in_place && device_alias(t->shards[o].data, &d);
-        alias[{t, o}] = d;
-      }
+    for (size_t p = 0; p < n; ++p) {
+      uint8_t* data = t->shards[p < k ? t->plan->in[p] : t->plan->out[p - k]].data;
+      rows[p] = mem == CFSEC_MEM_HOST ? nullptr : data;
+      if (mem == CFSEC_MEM_HOST) in_place = in_place && device_alias(data, &rows[p]);
     }
-    (in_place ? direct : staged).push_back(t);
+    (in_place ? direct.tasks : staged).push_back(t);
+    if (in_place) direct.rows.push_back(rows);
+    rows += n;
   }
-  if (async && (!staged.empty() || (checks && !async->flags))) return CFSEC_ERR_INVALID_ARG;
-  // staging lanes: each holds whole stripes, at least the largest one
-  size_t lane_bytes = 0, staged_total = 0;
-  for (StripeTask* t : staged) {
-    const size_t b = align_up(t->len, kSlot) * (t->plan->in.size() + t->plan->out.size());
+}
+
+// Staging lanes: each holds whole stripes, at least the largest one.
+void BatchRun::size_lanes() {
+  for (const StripeTask* t : staged) {
+    const size_t b = align_up(t->len, kSlotAlign) * (t->plan->in.size() + t->plan->out.size());
     lane_bytes = std::max(lane_bytes, b);
     staged_total += b;
   }
   if (!staged.empty()) lane_bytes = std::max(lane_bytes, std::min(kLaneBudget, staged_total));
   // two lanes only for staged chunks (a second phase of in-place stripes follows the first on one
   // stream)
-  const int nlanes = !staged.empty() && (staged_total > lane_bytes || nphase > 1) ? 2 : 1;
-  DeviceContext::Workspace* ws = nullptr;
-  Status st = ctx->acquire(lane_bytes * nlanes, (size_t)std::max(n, nitems), &ws, (size_t)n,
-                           sums && !async ? crc->n : 0);
+  nlanes = !staged.empty() && (staged_total > lane_bytes || nphase > 1) ? 2 : 1;
+}
+
+Status BatchRun::acquire(DeviceContext* ctx, size_t ntasks) {
+  const Status st = ctx->acquire(lane_bytes * nlanes, std::max(ntasks, (size_t)nitems), &ws, ntasks,
+                                 sums && !async ? crc->n : 0);
   if (st != CFSEC_OK) return st;
-  // checksum words: the caller's device array (asynchronous) or the workspace's, zeroed first (the
-  // CRC kernel XOR-accumulates)
-  uint32_t* dcrc = !sums ? nullptr : async ? crc->words : ws->dcrc;
-  // asynchronous calls run on the caller's stream (NULL: the legacy default stream); synchronous
-  // ones on the workspace's streams, ordered after the legacy default stream for device memory
-  hipStream_t lane[2] = {async ? async->stream : ws->stream, ws->stream2};
-  // lane `to` waits for everything queued on lane `from` so far
-  const auto join = [&](int from, int to) {
-    Status e = hip_status(hipEventRecord(ws->ev, lane[from]), "hipEventRecord");
-    if (e == CFSEC_OK) e = hip_status(hipStreamWaitEvent(lane[to], ws->ev, 0), "hipStreamWaitEvent");
-    return e;
-  };
+  dcrc = !sums ? nullptr : async ? crc->words : ws->dcrc;
+  lane[0] = async ? async->stream : ws->stream;
+  lane[1] = ws->stream2;
+  return CFSEC_OK;
+}
+
+// Order the lanes, zero the checksum words and choose where the Verify flags go.
+Status BatchRun::begin(DeviceContext* ctx, int mem, const std::vector<StripeTask*>& tasks) {
+  Status st = CFSEC_OK;
   if (mem == CFSEC_MEM_DEVICE && !async) st = ctx->order_after_default(ws);
   // Zeroed inline on lane 0: a memset on lane 1 beside the first products, waited for by the first
   // checksum launch, measured slower (C5 +26 instead of +14 us, EC12P4 fused encode + CRC 246
   // instead of 224 us: the cross-stream wait costs more than the 10 KiB fill it hides).  When the
   // first launch is a 16x16-dyadic repair (C5's tasklet) its workgroup (0, 0) zeroes the words and
-  // the memset launch goes (zero_first below).
-  bool zero_first = false;
-  if (sums && nlanes == 1 && nphase == 1 && !direct.empty()) {
-    const StripeTask* t0 = direct.front();
+  // the memset launch goes (zero_first, handed to launch_part).
+  if (sums && nlanes == 1 && nphase == 1 && !direct.tasks.empty()) {
+    const StripeTask* t0 = direct.tasks.front();
     zero_first = t0->plan->dy16 && t0->phase == 0 && crc->n <= 0xFFFFFFFFu;
   }
   if (st == CFSEC_OK && sums && !zero_first)
     st = hip_status(hipMemsetAsync(dcrc, 0, crc->n * 4, lane[0]), "hipMemsetAsync(crc)");
   if (st == CFSEC_OK && nlanes > 1) st = join(0, 1);
-  // crc32.ChecksumIEEE of the rows the tasks of a launched part name, on the part's stream, from the
-  // same device addresses the product used (staged rows before their lane is reused)
-  const auto checksum = [&](const std::vector<StripeTask*>& part, auto ptr, hipStream_t s) -> Status {
-    if (!sums) return CFSEC_OK;
-    std::map<size_t, std::pair<std::vector<const uint8_t*>, std::vector<uint32_t>>> by_len;
-    for (StripeTask* t : part) {
-      if (!t->crc || t->len == 0) continue;
-      auto& v = by_len[t->len];
-      const auto add = [&](int row) {
-        const int64_t w = t->crc_word + (t->crc_map ? t->crc_map[row] : row);
-        if (w < 0 || (size_t)w >= crc->n) return;
-        v.first.push_back(ptr(t, row));
-        v.second.push_back((uint32_t)w);
-      };
-      if (t->crc == 2)
-        for (int c : t->plan->in) add(c);
-      for (int r = 0; r < t->plan->nstore; ++r) add(t->plan->out[r]);
-    }
-    for (auto& kv : by_len) {
-      const Status e = hip_status(launch_crc32_to(kv.second.first.data(), kv.first, (int)kv.second.first.size(), dcrc,
-                                                  kv.second.second.data(), crc32_shift_ones(kv.first), s),
-                                  "launch_crc32_to(batch)");
-      if (e != CFSEC_OK) return e;
-    }
-    return CFSEC_OK;
-  };
-  std::map<int, int> tasks_per_owner;  // a bid with several checksummed tasks keeps the separate pass
-  for (StripeTask* t : tasks)          // (EnableVerify's compare task writes no words: not counted)
-    if (t->crc) ++tasks_per_owner[t->owner];
-  int next_flag = 0;
   // Verify flags.  A group whose tasks belong to consecutive items writes each mismatch straight
   // into the items' words -- the caller's device array (asynchronous) or the pinned host words,
   // zeroed here first (synchronous) -- so no gather launch follows it (C4 / C5: one tasklet group,
@@ -895,155 +918,173 @@ Status RSEngine::run_device(std::vector<StripeTask*>& tasks, int mem, DeviceCont
     const char* v = std::getenv("CFSEC_BATCH_DIRECT_FLAGS");
     return !(v && v[0] == '0');
   }();
-  uint32_t* fdirect = checks && kDirect ? (async ? async->flags : ws->hflags_dev) : nullptr;
+  fdirect = checks && kDirect ? (async ? async->flags : ws->hflags_dev) : nullptr;
   if (fdirect && !async)
-    for (StripeTask* t : tasks) ws->hflags[t->owner] = 0;
-  const auto route = [&](std::vector<Group>& groups) {
-    if (!fdirect) return;
-    for (Group& gr : groups) {
-      if (gr.plan->out.size() <= (size_t)gr.plan->nstore) continue;  // nothing compared
-      bool consecutive = true;
-      for (size_t i = 1; i < gr.tasks.size() && consecutive; ++i)
-        consecutive = gr.tasks[i]->owner == gr.tasks[0]->owner + (int)i;
-      if (consecutive) gr.direct = fdirect + gr.tasks[0]->owner;
+    for (const StripeTask* t : tasks) ws->hflags[t->owner] = 0;
+  return st;
+}
+
+// One phase: its in-place tasks as one part on lane 0, then its staged tasks in chunks.  The in-place
+// part alone tries the launches that checksum within the product's pass (launch_part's fuse_crc).
+Status BatchRun::run_phase(int ph) {
+  Status st = CFSEC_OK;
+  if (ph > 0 && nlanes > 1) {  // a phase starts after everything of the previous one, on both lanes
+    st = join(1, 0);
+    if (st == CFSEC_OK) st = join(0, 1);
+  }
+  Part dph;
+  std::vector<StripeTask*> sph;
+  for (size_t i = 0; i < direct.tasks.size(); ++i)
+    if (direct.tasks[i]->phase == ph) {
+      dph.tasks.push_back(direct.tasks[i]);
+      dph.rows.push_back(direct.rows[i]);
     }
+  for (StripeTask* t : staged)
+    if (t->phase == ph) sph.push_back(t);
+  if (st == CFSEC_OK && !dph.tasks.empty()) st = launch_part(dph, lane[0], /*fuse_crc=*/true);
+  if (st == CFSEC_OK) st = run_staged(sph);
+  return st;
+}
+
+// Staged stripes: chunks of whole stripes alternating over the two lanes; each lane copies its
+// chunk in, runs it and copies the stored rows back while the other lane's chunk moves.
+Status BatchRun::run_staged(const std::vector<StripeTask*>& sph) {
+  Status st = CFSEC_OK;
+  std::vector<size_t> off;
+  std::vector<uint8_t*> slot;
+  const auto copy = [&](uint8_t* dst, const uint8_t* src, size_t len, hipMemcpyKind kind, hipStream_t s) {
+    if (st == CFSEC_OK)
+      st = hip_status(hipMemcpyAsync(dst, src, len, kind, s),
+                      kind == hipMemcpyHostToDevice ? "hipMemcpyAsync H2D" : "hipMemcpyAsync D2H");
   };
-  std::vector<std::pair<StripeTask*, int>> flags;  // (task, flag word; -1: written directly)
-  const auto record = [&](const std::vector<Group>& groups) {
-    for (const Group& gr : groups)
-      for (size_t i = 0; i < gr.tasks.size(); ++i) flags.emplace_back(gr.tasks[i], gr.direct ? -1 : gr.flag0 + (int)i);
-  };
-  int chunk = 0;
-  tm.reset(new HostTimer("    group + launch"));
-  for (int ph = 0; ph < nphase && st == CFSEC_OK; ++ph) {
-    if (ph > 0 && nlanes > 1) {  // a phase starts after everything of the previous one, on both lanes
-      st = join(1, 0);
-      if (st == CFSEC_OK) st = join(0, 1);
+  for (size_t i0 = 0; st == CFSEC_OK && i0 < sph.size(); ++chunk) {
+    hipStream_t s = lane[chunk % nlanes];
+    uint8_t* base = ws->dbuf + lane_bytes * (chunk % nlanes);
+    const size_t i1 = pack_chunk(sph.data(), sph.size(), i0, lane_bytes, &off);
+    slot.resize(off.size());
+    for (size_t j = 0; j < off.size(); ++j) slot[j] = base + off[j];
+    Part part;
+    part.tasks.assign(sph.begin() + i0, sph.begin() + i1);
+    uint8_t** rows = slot.data();
+    for (const StripeTask* t : part.tasks) {  // the inputs and the compared rows go in
+      const StripePlan& p = *t->plan;
+      const size_t k = p.in.size();
+      part.rows.push_back(rows);
+      for (size_t c = 0; c < k; ++c) copy(rows[c], t->shards[p.in[c]].data, t->len, hipMemcpyHostToDevice, s);
+      for (size_t r = p.nstore; r < p.out.size(); ++r)
+        copy(rows[k + r], t->shards[p.out[r]].data, t->len, hipMemcpyHostToDevice, s);
+      rows += k + p.out.size();
     }
-    // in-place stripes: one set of launches on lane 0
-    std::vector<StripeTask*> dph, sph;
-    for (StripeTask* t : direct)
-      if (t->phase == ph) dph.push_back(t);
-    for (StripeTask* t : staged)
-      if (t->phase == ph) sph.push_back(t);
-    if (st == CFSEC_OK && !dph.empty()) {
-      const auto dptr = [&](const StripeTask* t, int idx) {
-        return mem == CFSEC_MEM_DEVICE ? (const uint8_t*)t->shards[idx].data : (const uint8_t*)alias[{t, idx}];
-      };
-      std::unique_ptr<HostTimer> gt(new HostTimer("      make_groups"));
-      std::vector<Group> groups = make_groups(dph, &next_flag, dptr);
-      route(groups);
-      gt.reset();
-      // dy16 groups that checksum their rebuilt rows in the repair pass itself
-      std::vector<std::vector<char>> crc_done(groups.size());
-      bool any_crc_fused = false;
-      if (sums)
-        for (size_t gi = 0; gi < groups.size(); ++gi)
-          any_crc_fused |= dy16_crc_group(groups[gi], dcrc, crc->n, tasks_per_owner, &crc_done[gi]);
-      if (zero_first) {  // make_groups keeps first-appearance order: groups[0] holds direct.front()
-        if (!groups.empty() && groups[0].plan->dy16 && !any_crc_fused) {
-          groups[0].zero_words = dcrc;
-          groups[0].nzero = (uint32_t)crc->n;
-        } else {  // (the repair pass's checksum atomics must find the words zeroed already)
-          st = hip_status(hipMemsetAsync(dcrc, 0, crc->n * 4, lane[0]), "hipMemsetAsync(crc)");
-        }
-        zero_first = false;
-      }
-      std::set<const StripeTask*> fused;  // tasks whose checksums a fused product + CRC launch took
-      for (size_t gi = 0; gi < groups.size(); ++gi) {
-        const Group& gr = groups[gi];
-        if (st != CFSEC_OK) break;
-        if (sums && fused_crc_group(gr, dcrc, crc->n, tasks_per_owner, lane[0], &st)) {
-          fused.insert(gr.tasks.begin(), gr.tasks.end());
-          continue;
-        }
-        {
-          HostTimer lt("      launch_group");
-          st = hip_status(launch_group(gr, ws->bflags, lane[0]), "launch_matvec(batch)");
-        }
-        if (gr.crc_done) {
-          int nf = 0;
-          for (size_t i = 0; i < gr.tasks.size(); ++i)
-            if ((*gr.crc_done)[i]) {
-              fused.insert(gr.tasks[i]);
-              ++nf;
-            }
-          if (std::getenv("CFSEC_TRACE_BATCH"))
-            std::fprintf(stderr, "cfsec batch: repair-pass crc group tasks=%zu fused=%d\n", gr.tasks.size(), nf);
-        }
-      }
-      record(groups);
-      if (st == CFSEC_OK) {
-        std::vector<StripeTask*> rest;
-        for (StripeTask* t : dph)
-          if (!fused.count(t)) rest.push_back(t);
-        st = checksum(rest, dptr, lane[0]);
-      }
+    if (st == CFSEC_OK) st = launch_part(part, s, /*fuse_crc=*/false);
+    for (size_t i = 0; i < part.tasks.size(); ++i) {  // the stored rows come back
+      const StripeTask* t = part.tasks[i];
+      for (int r = 0; r < t->plan->nstore; ++r)
+        copy(t->shards[t->plan->out[r]].data, part.rows[i][t->plan->in.size() + r], t->len, hipMemcpyDeviceToHost, s);
     }
-    // staged stripes: chunks of whole stripes alternating over the two lanes; each lane copies its
-    // chunk in, runs it and copies the stored rows back while the other lane's chunk moves
-    size_t i0 = 0;
-    for (; st == CFSEC_OK && i0 < sph.size(); ++chunk) {
-      const int l = chunk % nlanes;
-      hipStream_t s = lane[l];
-      uint8_t* base = ws->dbuf + lane_bytes * l;
-      size_t used = 0, i1 = i0;
-      std::map<std::pair<const StripeTask*, int>, uint8_t*> slot;
-      while (i1 < sph.size()) {
-        StripeTask* t = sph[i1];
-        const size_t sl = align_up(t->len, kSlot);
-        const size_t need = sl * (t->plan->in.size() + t->plan->out.size());
-        if (i1 > i0 && used + need > lane_bytes) break;
-        for (int c : t->plan->in) {
-          slot[{t, c}] = base + used;
-          used += sl;
-        }
-        for (int o : t->plan->out) {
-          slot[{t, o}] = base + used;
-          used += sl;
-        }
-        ++i1;
+    i0 = i1;
+  }
+  return st;
+}
+
+// Launch one part on stream s: make its groups, route their Verify flags, launch them, record the
+// flag words, then checksum the rows no launch checksummed (crc32.ChecksumIEEE, from the device
+// addresses the product used; staged rows before their lane is reused).
+// fuse_crc: try the launches that checksum within the product's own pass -- fused_crc_group,
+// dy16_crc_group and, for the call's first launch, the dy16 repair that zeroes the words itself
+// (zero_first).  On for the in-place part, off for staged chunks, whose rows take the separate pass.
+Status BatchRun::launch_part(const Part& part, hipStream_t s, bool fuse_crc) {
+  Status st = CFSEC_OK;
+  std::vector<Group> groups;
+  {
+    HostTimer gt("      make_groups");
+    groups = make_groups(part, &next_flag);
+    if (fdirect)
+      for (Group& gr : groups) {
+        if (!gr.plan->compares()) continue;  // nothing compared
+        bool consecutive = true;
+        for (size_t i = 1; i < gr.tasks.size() && consecutive; ++i)
+          consecutive = gr.tasks[i]->owner == gr.tasks[0]->owner + (int)i;
+        if (consecutive) gr.direct = fdirect + gr.tasks[0]->owner;
       }
-      std::vector<StripeTask*> part(sph.begin() + i0, sph.begin() + i1);
-      for (StripeTask* t : part) {
-        for (int c : t->plan->in)
-          if (st == CFSEC_OK)
-            st = hip_status(hipMemcpyAsync(slot[{t, c}], t->shards[c].data, t->len, hipMemcpyHostToDevice, s),
-                            "hipMemcpyAsync H2D");
-        for (size_t r = t->plan->nstore; r < t->plan->out.size(); ++r)
-          if (st == CFSEC_OK) {
-            const int o = t->plan->out[r];
-            st = hip_status(hipMemcpyAsync(slot[{t, o}], t->shards[o].data, t->len, hipMemcpyHostToDevice, s),
-                            "hipMemcpyAsync H2D");
-          }
-      }
-      const auto sptr = [&](const StripeTask* t, int idx) { return (const uint8_t*)slot[{t, idx}]; };
-      std::vector<Group> groups = make_groups(part, &next_flag, sptr);
-      route(groups);
-      for (const Group& gr : groups)
-        if (st == CFSEC_OK) st = hip_status(launch_group(gr, ws->bflags, s), "launch_matvec(batch)");
-      record(groups);
-      if (st == CFSEC_OK) st = checksum(part, sptr, s);
-      for (StripeTask* t : part)
-        for (int r = 0; r < t->plan->nstore && st == CFSEC_OK; ++r) {
-          const int o = t->plan->out[r];
-          st = hip_status(hipMemcpyAsync(t->shards[o].data, slot[{t, o}], t->len, hipMemcpyDeviceToHost, s),
-                          "hipMemcpyAsync D2H");
+  }
+  fuse_crc = fuse_crc && sums;
+  // dy16 groups that checksum their rebuilt rows in the repair pass itself
+  std::vector<std::vector<char>> crc_done(groups.size());
+  bool any_crc_fused = false;
+  if (fuse_crc)
+    for (size_t gi = 0; gi < groups.size(); ++gi)
+      any_crc_fused |= dy16_crc_group(groups[gi], dcrc, crc->n, tasks_per_owner, &crc_done[gi]);
+  if (fuse_crc && zero_first) {  // make_groups keeps first-appearance order: groups[0] holds direct.front()
+    if (!groups.empty() && groups[0].plan->dy16 && !any_crc_fused) {
+      groups[0].zero_words = dcrc;
+      groups[0].nzero = (uint32_t)crc->n;
+    } else {  // (the repair pass's checksum atomics must find the words zeroed already)
+      st = hip_status(hipMemsetAsync(dcrc, 0, crc->n * 4, s), "hipMemsetAsync(crc)");
+    }
+    zero_first = false;
+  }
+  std::vector<char> taken(part.tasks.size(), 0);  // tasks whose checksums a launch took
+  for (const Group& gr : groups) {
+    if (st != CFSEC_OK) break;
+    if (fuse_crc && fused_crc_group(gr, dcrc, crc->n, tasks_per_owner, s, &st)) {
+      for (size_t i : gr.at) taken[i] = 1;
+      continue;
+    }
+    {
+      HostTimer lt("      launch_group");
+      st = hip_status(launch_group(gr, ws->bflags, s), "launch_matvec(batch)");
+    }
+    if (gr.crc_done) {
+      int nf = 0;
+      for (size_t i = 0; i < gr.tasks.size(); ++i)
+        if ((*gr.crc_done)[i]) {
+          taken[gr.at[i]] = 1;
+          ++nf;
         }
-      i0 = i1;
+      if (std::getenv("CFSEC_TRACE_BATCH"))
+        std::fprintf(stderr, "cfsec batch: repair-pass crc group tasks=%zu fused=%d\n", gr.tasks.size(), nf);
     }
   }
+  for (const Group& gr : groups)
+    for (size_t i = 0; i < gr.tasks.size(); ++i) flags.emplace_back(gr.tasks[i], gr.direct ? -1 : gr.flag0 + (int)i);
+  if (st == CFSEC_OK) st = checksum(part, taken, s);
+  return st;
+}
+
+// The separate checksum pass over the tasks of a part no launch has taken: one launch per length.
+Status BatchRun::checksum(const Part& part, const std::vector<char>& taken, hipStream_t s) {
+  if (!sums) return CFSEC_OK;
+  std::map<size_t, std::pair<std::vector<const uint8_t*>, std::vector<uint32_t>>> by_len;
+  for (size_t i = 0; i < part.tasks.size(); ++i) {
+    const StripeTask* t = part.tasks[i];
+    if (taken[i] || !t->crc || t->len == 0) continue;
+    auto& v = by_len[t->len];
+    for_each_crc_row(*t, crc->n, [&](size_t p, size_t w) {
+      v.first.push_back(part.rows[i][p]);
+      v.second.push_back((uint32_t)w);
+    });
+  }
+  for (auto& kv : by_len) {
+    const Status e = hip_status(launch_crc32_to(kv.second.first.data(), kv.first, (int)kv.second.first.size(), dcrc,
+                                                kv.second.second.data(), crc32_shift_ones(kv.first), s),
+                                "launch_crc32_to(batch)");
+    if (e != CFSEC_OK) return e;
+  }
+  return CFSEC_OK;
+}
+
+// After the last phase, on lane 0 behind both lanes: the checksum words to the pinned mirror, and
+// the Verify flags per batch item, gathered from the per-task words (which the gather resets): into
+// the caller's device array (asynchronous), or straight into the pinned host words (no D2H copy).
+Status BatchRun::gather(Status st) {
   if (st == CFSEC_OK && nlanes > 1) st = join(1, 0);
   if (st == CFSEC_OK && sums && !async)
     st = hip_status(hipMemcpyAsync(ws->hcrc, ws->dcrc, crc->n * 4, hipMemcpyDeviceToHost, lane[0]),
                     "hipMemcpyAsync D2H(crc)");
-  // Verify flags per batch item, gathered from the per-task words (which the gather resets): into
-  // the caller's device array (asynchronous), or straight into the pinned host words (no D2H copy)
   if (st == CFSEC_OK && checks) {
     std::vector<std::pair<int, int>> pairs;
     for (auto& f : flags)
-      if (f.second >= 0 && f.first->plan->out.size() > (size_t)f.first->plan->nstore)
-        pairs.emplace_back(f.first->owner, f.second);
+      if (f.second >= 0 && f.first->plan->compares()) pairs.emplace_back(f.first->owner, f.second);
     std::sort(pairs.begin(), pairs.end());
     std::vector<int> item(pairs.size()), word(pairs.size());
     for (size_t i = 0; i < pairs.size(); ++i) item[i] = pairs[i].first, word[i] = pairs[i].second;
@@ -1052,34 +1093,54 @@ Status RSEngine::run_device(std::vector<StripeTask*>& tasks, int mem, DeviceCont
                     "launch_flag_gather");
   }
   if (st != CFSEC_OK) ws->bflags_clean = false;  // some task words may be left set: memset on reuse
+  return st;
+}
+
+// A synchronous call's results, once its lanes are done: a false Verify into the tasks' statuses,
+// the checksum words to the caller.
+void BatchRun::hand_back(const std::vector<StripeTask*>& tasks) {
+  if (checks)
+    for (auto& f : flags)
+      if (f.first->plan->compares() && ws->hflags[f.first->owner] != 0 && *f.first->status == CFSEC_OK)
+        *f.first->status = CFSEC_ERR_VERIFY;
+  if (sums)  // this device's words only (another device of the call fills the rest)
+    for (const StripeTask* t : tasks)
+      for_each_crc_row(*t, crc->n, [&](size_t, size_t w) { crc->words[w] = ws->hcrc[w]; });
+}
+
+}  // namespace
+
+// A batch call on one device: classify the tasks, size the lanes, acquire and zero, run the phases
+// (each: the in-place part, then the staged chunks), gather the flags, sync, hand back the results.
+Status RSEngine::run_device(std::vector<StripeTask*>& tasks, int mem, DeviceContext* ctx, const AsyncOut* async,
+                            const CrcOut* crc) {
+  HostTimer whole("  run_device");
+  std::unique_ptr<HostTimer> tm(new HostTimer("    classify + acquire"));
+  DeviceGuard g(ctx->device());
+  if (!g.ok()) return hip_status(hipErrorInvalidDevice, "hipSetDevice");
+  BatchRun run{async, crc};
+  run.classify(tasks, mem);
+  if (async && (!run.staged.empty() || (run.checks && !async->flags))) return CFSEC_ERR_INVALID_ARG;
+  run.size_lanes();
+  Status st = run.acquire(ctx, tasks.size());
+  if (st != CFSEC_OK) return st;
+  st = run.begin(ctx, mem, tasks);
+  tm.reset(new HostTimer("    group + launch"));
+  for (int ph = 0; ph < run.nphase && st == CFSEC_OK; ++ph) st = run.run_phase(ph);
+  st = run.gather(st);
   if (async) {
     tm.reset();
-    ctx->release_after(ws, lane[0]);
+    ctx->release_after(run.ws, run.lane[0]);
     return st;
   }
   tm.reset(new HostTimer("    sync"));
-  for (int l = 0; l < nlanes; ++l) {
-    const Status sync = ctx->finish(ws, lane[l]);
+  for (int l = 0; l < run.nlanes; ++l) {
+    const Status sync = ctx->finish(run.ws, run.lane[l]);
     if (st == CFSEC_OK) st = sync;
   }
   tm.reset();
-  if (st == CFSEC_OK && checks)
-    for (auto& f : flags)
-      if (f.first->plan->out.size() > (size_t)f.first->plan->nstore && ws->hflags[f.first->owner] != 0 &&
-          *f.first->status == CFSEC_OK)
-        *f.first->status = CFSEC_ERR_VERIFY;
-  if (st == CFSEC_OK && sums)  // this device's words only (another device of the call fills the rest)
-    for (StripeTask* t : tasks) {
-      if (!t->crc) continue;
-      const auto put = [&](int row) {
-        const int64_t w = t->crc_word + (t->crc_map ? t->crc_map[row] : row);
-        if (w >= 0 && (size_t)w < crc->n) crc->words[w] = ws->hcrc[w];
-      };
-      if (t->crc == 2)
-        for (int c : t->plan->in) put(c);
-      for (int r = 0; r < t->plan->nstore; ++r) put(t->plan->out[r]);
-    }
-  ctx->release(ws);
+  if (st == CFSEC_OK) run.hand_back(tasks);
+  ctx->release(run.ws);
   return st;
 }
 
@@ -1141,11 +1202,7 @@ Status ECEncoder::reconstruct_batch(cfsec_shard* shards, int n, int nbids, const
     PlanStore store;
     std::vector<StripeTask> tasks;
     engine_->plan_reconstruct_tasks(stripes.data(), (int)stripes.size(), verify, st.data(), 0, 0, &store, &tasks);
-    for (auto& t : tasks) {
-      t.owner = pos[t.owner];  // the bid: its verify word
-      t.crc = crc ? 1 : 0;     // the rebuilt shards' checksums (blobnode ShardCrc32)
-      t.crc_word = (int64_t)t.owner * n;
-    }
+    stamp_items(tasks, pos, crc, n);
     rc = engine_->run_stripes(tasks, mem, async, crc);
   }
   for (size_t i = 0; i < pos.size(); ++i) status[pos[i]] = st[i];
@@ -1208,11 +1265,7 @@ Status LrcEncoder::reconstruct_batch(cfsec_shard* shards, int n, int nbids, cons
     PlanStore store;
     std::vector<StripeTask> tasks;
     local_->plan_reconstruct_tasks(stripes.data(), (int)stripes.size(), verify, st.data(), 0, 0, &store, &tasks);
-    for (auto& t : tasks) {
-      t.owner = pos[t.owner];
-      t.crc = crc ? 1 : 0;
-      t.crc_word = (int64_t)t.owner * n;
-    }
+    stamp_items(tasks, pos, crc, n);
     const Status rc = local_->run_stripes(tasks, mem, async, crc);
     for (size_t i = 0; i < pos.size(); ++i) status[pos[i]] = st[i];
     clear_failed_crcs(crc, async, status, nbids, n);
@@ -1308,11 +1361,7 @@ Status LrcEncoder::reconstruct_batch(cfsec_shard* shards, int n, int nbids, cons
     tasks[t].crc_map = idc[vaz[v]].data();  // local index -> global shard index
   }
   ph.reset();
-  for (auto& t : tasks) {
-    t.owner = pos[t.owner];  // the bid: its device, its verify word
-    t.crc = crc ? 1 : 0;     // rebuilt shards, global or local (blobnode ShardCrc32)
-    t.crc_word = (int64_t)t.owner * n;
-  }
+  stamp_items(tasks, pos, crc, n);  // the bid: its device, its verify word; rebuilt shards, global or local
   const Status rc = engine_->run_stripes(tasks, mem, async, crc);
   // per bid: a Reconstruct error (global, then local) wins over a failed Verify
   std::vector<int> local_err(stripes.size(), CFSEC_OK);
@@ -1359,13 +1408,8 @@ Status ECEncoder::encode_batch(cfsec_shard* shards, int n, int nstripes, int mem
     for (size_t i = 0; i < pos.size(); ++i) status[pos[i]] = st[i];
     return rc;
   }
-  StripePlan plan;
-  for (int i = 0; i < k; ++i) plan.in.push_back(i);
-  for (int i = k; i < tot; ++i) plan.out.push_back(i);
-  plan.nstore = m;
-  plan.rows = engine_->matrix_rows(k, m);
-  StripePlan vplan = plan;
-  vplan.nstore = 0;
+  const StripePlan plan = whole_stripe_plan(k, tot, engine_->matrix_rows(k, m), m);
+  const StripePlan vplan = whole_stripe_plan(k, tot, plan.rows, 0);
   std::vector<StripeTask> tasks;
   for (int s = 0; s < nstripes; ++s) {
     status[s] = CFSEC_OK;
@@ -1375,9 +1419,7 @@ Status ECEncoder::encode_batch(cfsec_shard* shards, int n, int nstripes, int mem
       continue;
     }
     size_t S = 0;
-    Status st = stripe_size(sh, n, false, &S);
-    for (int i = 0; i < n && st == CFSEC_OK; ++i)
-      if (!sh[i].data) st = CFSEC_ERR_INVALID_ARG;
+    const Status st = whole_stripe_ok(sh, n, &S);
     if (st != CFSEC_OK) {
       status[s] = st;
       continue;
@@ -1410,11 +1452,8 @@ Status LrcEncoder::encode_batch(cfsec_shard* shards, int n, int nstripes, int me
     }
     return CFSEC_OK;
   }
-  StripePlan plan;
-  for (int i = 0; i < N; ++i) plan.in.push_back(i);
-  for (int i = N; i < N + M + L; ++i) plan.out.push_back(i);
-  plan.nstore = M + L;
-  plan.rows = fused_;
+  const StripePlan plan = whole_stripe_plan(N, N + M + L, fused_, M + L);
+  const StripePlan vplan = whole_stripe_plan(N, N + M + L, fused_, 0);
   std::vector<StripeTask> tasks;
   for (int s = 0; s < nstripes; ++s) {
     status[s] = CFSEC_OK;
@@ -1425,10 +1464,8 @@ Status LrcEncoder::encode_batch(cfsec_shard* shards, int n, int nstripes, int me
     }
     Status st = fill_full_shards(sh, n);
     size_t S = 0;
-    if (st == CFSEC_OK) st = stripe_size(sh, n, false, &S);
-    for (int i = 0; i < n && st == CFSEC_OK; ++i)
-      if (!sh[i].data) st = CFSEC_ERR_INVALID_ARG;
-    if (st == CFSEC_ERR_SHARD_SIZE && stripe_size(sh, N + M, false, &S) == CFSEC_OK) {
+    if (st == CFSEC_OK) st = whole_stripe_ok(sh, n, &S);
+    if (st == CFSEC_ERR_SHARD_SIZE && check_shards(sh, N + M, false, &S) == CFSEC_OK) {
       // only a local shard has another length: the reference still writes the global parity and
       // the AZs that pass their check -- the single-stripe path restates that sequence
       status[s] = encode_stripe(sh, n, mem, async ? async->stream : nullptr);
@@ -1442,8 +1479,6 @@ Status LrcEncoder::encode_batch(cfsec_shard* shards, int n, int nstripes, int me
     tasks.back().crc = crc ? 2 : 0;  // every shard, global and local (access/stream_put.go:249-253)
     tasks.back().crc_word = (int64_t)s * n;
   }
-  StripePlan vplan = plan;
-  vplan.nstore = 0;
   if (enable_verify_) {  // the Verify pass in the same call, after the encode (phase 1)
     const size_t ne = tasks.size();
     for (size_t i = 0; i < ne; ++i) {

@@ -15,9 +15,14 @@ namespace cfsec {
 
 namespace {
 thread_local std::string t_last_error;
-constexpr size_t kSlotAlign = 256;  // staging rows start on 256-B boundaries
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+size_t first_size(const cfsec_shard* shards, int n) {
+  for (int i = 0; i < n; ++i)
+    if (shards[i].len != 0) return shards[i].len;
+  return 0;
+}
+
+}  // namespace
 
 // KRS/reedsolomon.go:1314-1339 checkShards / shardSize.
 Status check_shards(const cfsec_shard* shards, int n, bool nilok, size_t* size) {
@@ -33,14 +38,6 @@ Status check_shards(const cfsec_shard* shards, int n, bool nilok, size_t* size) 
   *size = s;
   return CFSEC_OK;
 }
-
-size_t first_size(const cfsec_shard* shards, int n) {
-  for (int i = 0; i < n; ++i)
-    if (shards[i].len != 0) return shards[i].len;
-  return 0;
-}
-
-}  // namespace
 
 // ec.fillFullShards (encoder.go:199-210).  Go allocates when cap is short; across the
 // C ABI the caller must hand in buffers with enough capacity.
@@ -98,6 +95,11 @@ Status hip_status(hipError_t e, const char* what) {
   if (e == hipSuccess) return CFSEC_OK;
   set_last_error(std::string(what) + ": " + hipGetErrorString(e));
   return CFSEC_ERR_DEVICE;
+}
+
+Status lane_wait(hipEvent_t ev, hipStream_t from, hipStream_t to) {
+  const Status e = hip_status(hipEventRecord(ev, from), "hipEventRecord");
+  return e != CFSEC_OK ? e : hip_status(hipStreamWaitEvent(to, ev, 0), "hipStreamWaitEvent");
 }
 
 // ---------------------------------------------------------------- devices
@@ -537,26 +539,29 @@ Status RSEngine::run(const Matrix& rows, const std::vector<cfsec_shard*>& ins,
     const size_t total = S * (size_t)(nin + nout);
     if (!two_step_verify && total <= kSmallPageable) {
       std::pair<uint8_t*, size_t> stage = pinned_stage_take(total);
-      if (stage.first) {
+      // the stage's device address, resolved once: the inner call is a device-memory call on it (one
+      // level, whatever happens); a stage the GPU cannot address goes back and run_host takes the call
+      uint8_t* dstage = nullptr;
+      if (stage.first && device_alias(stage.first, &dstage)) {
         std::vector<cfsec_shard> sin(nin), sout(nout);
         std::vector<cfsec_shard*> pin(nin), pout(nout);
         for (int i = 0; i < nin; ++i) {
           std::memcpy(stage.first + S * i, ins[i]->data, S);
-          sin[i] = cfsec_shard{stage.first + S * i, S, S};
+          sin[i] = cfsec_shard{dstage + S * i, S, S};
           pin[i] = &sin[i];
         }
         for (int r = 0; r < nout; ++r) {
-          uint8_t* d = stage.first + S * (nin + r);
-          if (mode != MatVecMode::kStore) std::memcpy(d, outs[r]->data, S);
-          sout[r] = cfsec_shard{d, S, S};
+          if (mode != MatVecMode::kStore) std::memcpy(stage.first + S * (nin + r), outs[r]->data, S);
+          sout[r] = cfsec_shard{dstage + S * (nin + r), S, S};
           pout[r] = &sout[r];
         }
-        Status st = run(rows, pin, pout, S, CFSEC_MEM_HOST, nullptr, mode, ok);
+        Status st = run(rows, pin, pout, S, CFSEC_MEM_DEVICE, nullptr, mode, ok);
         if (st == CFSEC_OK && mode != MatVecMode::kVerify)
-          for (int r = 0; r < nout; ++r) std::memcpy(outs[r]->data, sout[r].data, S);
+          for (int r = 0; r < nout; ++r) std::memcpy(outs[r]->data, stage.first + S * (nin + r), S);
         pinned_stage_give(stage);
         return st;
       }
+      pinned_stage_give(stage);
     }
     if (!two_step_verify) return run_host(rows, ins, outs, S, mode, ok);
   }
@@ -595,13 +600,7 @@ Status RSEngine::run(const Matrix& rows, const std::vector<cfsec_shard*>& ins,
   }
   if (st == CFSEC_OK && verify) st = hip_status(hipMemsetAsync(ws->dflags, 0, 4, s), "hipMemsetAsync");
   if (st == CFSEC_OK) {
-    MatVecJob job;
-    job.k = nin;
-    job.m = nout;
-    job.coef = rows.v.data();
-    job.len = S;
-    job.nstripes = 1;
-    job.in = din.data();
+    MatVecJob job = matvec_job(nin, nout, rows.v.data(), S, 1, din.data(), nullptr);
     job.flags = ws->dflags;
     if (!two_step_verify) {
       job.out = dout.data();
@@ -693,8 +692,7 @@ Status RSEngine::run_host(const Matrix& rows, const std::vector<cfsec_shard*>& i
   const int64_t in_stride = host_row_stride(ins), out_stride = host_row_stride(outs);
   if (verify) {
     st = hip_status(hipMemsetAsync(ws->dflags, 0, 4, lane[0]), "hipMemsetAsync");
-    if (st == CFSEC_OK && nlanes > 1) st = hip_status(hipEventRecord(ws->ev, lane[0]), "hipEventRecord");
-    if (st == CFSEC_OK && nlanes > 1) st = hip_status(hipStreamWaitEvent(lane[1], ws->ev, 0), "hipStreamWaitEvent");
+    if (st == CFSEC_OK && nlanes > 1) st = lane_wait(ws->ev, lane[0], lane[1]);
   }
   std::vector<const uint8_t*> din(nin);
   std::vector<uint8_t*> dout(nout);
@@ -709,14 +707,7 @@ Status RSEngine::run_host(const Matrix& rows, const std::vector<cfsec_shard*>& i
     if (st == CFSEC_OK && verify)
       st = hip_status(copy_rows(outs, out_stride, off, len, base + chunk * nin, chunk, true, s), "hipMemcpyAsync H2D");
     if (st == CFSEC_OK) {
-      MatVecJob job;
-      job.k = nin;
-      job.m = nout;
-      job.coef = rows.v.data();
-      job.len = len;
-      job.nstripes = 1;
-      job.in = din.data();
-      job.out = dout.data();
+      MatVecJob job = matvec_job(nin, nout, rows.v.data(), len, 1, din.data(), dout.data());
       job.mode = mode;
       job.flags = ws->dflags;
       st = hip_status(launch_matvec(job, s), "launch_matvec");
@@ -724,10 +715,7 @@ Status RSEngine::run_host(const Matrix& rows, const std::vector<cfsec_shard*>& i
     if (st == CFSEC_OK && !verify)
       st = hip_status(copy_rows(outs, out_stride, off, len, base + chunk * nin, chunk, false, s), "hipMemcpyAsync D2H");
   }
-  if (st == CFSEC_OK && verify && nlanes > 1) {
-    st = hip_status(hipEventRecord(ws->ev, lane[1]), "hipEventRecord");
-    if (st == CFSEC_OK) st = hip_status(hipStreamWaitEvent(lane[0], ws->ev, 0), "hipStreamWaitEvent");
-  }
+  if (st == CFSEC_OK && verify && nlanes > 1) st = lane_wait(ws->ev, lane[1], lane[0]);
   if (st == CFSEC_OK && verify)
     st = hip_status(hipMemcpyAsync(ws->hflags, ws->dflags, 4, hipMemcpyDeviceToHost, lane[0]), "hipMemcpyAsync D2H");
   for (int l = 0; l < nlanes; ++l) {
@@ -786,15 +774,8 @@ Status RSEngine::encode_crc(cfsec_shard* shards, int n, int mem, hipStream_t str
         st = hip_status(hipMemcpyAsync(dptr[i], shards[i].data, S, hipMemcpyHostToDevice, s), "hipMemcpyAsync H2D");
     }
   if (st == CFSEC_OK && m_ > 0) {
-    MatVecJob job;
-    job.k = k_;
-    job.m = m_;
-    job.coef = parity_.v.data();
-    job.len = S;
-    job.nstripes = 1;
     std::vector<const uint8_t*> in(dptr.begin(), dptr.begin() + k_);
-    job.in = in.data();
-    job.out = dptr.data() + k_;
+    const MatVecJob job = matvec_job(k_, m_, parity_.v.data(), S, 1, in.data(), dptr.data() + k_);
     std::vector<int> slots(n);
     for (int i = 0; i < n; ++i) slots[i] = i;
     st = matvec_with_crc(job, dptr.data(), n, slots, S, ws->dflags, s);
@@ -972,26 +953,50 @@ Status RSEngine::join(uint8_t* dst, size_t dst_len, const cfsec_shard* shards, i
   return CFSEC_OK;
 }
 
+namespace {
+// The rows of a pointer batch: stripe s's row i is ptrs[s * width + i].
+struct PtrTables {
+  std::vector<const uint8_t*> in;
+  std::vector<uint8_t*> out;
+};
+
+std::vector<int> index_range(int a, int b) {
+  std::vector<int> v;
+  for (int i = a; i < b; ++i) v.push_back(i);
+  return v;
+}
+
+// The in / out tables of a launch: the rows in_idx, then out_idx, of every stripe.
+PtrTables ptr_tables(uint8_t* const* ptrs, size_t width, int nstripes, const std::vector<int>& in_idx,
+                     const std::vector<int>& out_idx) {
+  const size_t k = in_idx.size(), m = out_idx.size();
+  PtrTables t{std::vector<const uint8_t*>(size_t(nstripes) * k), std::vector<uint8_t*>(size_t(nstripes) * m)};
+  for (int s = 0; s < nstripes; ++s) {
+    for (size_t c = 0; c < k; ++c) t.in[size_t(s) * k + c] = ptrs[size_t(s) * width + in_idx[c]];
+    for (size_t r = 0; r < m; ++r) t.out[size_t(s) * m + r] = ptrs[size_t(s) * width + out_idx[r]];
+  }
+  return t;
+}
+
+// present[i] = shard i is not among erased[0 .. nerased); false for an index outside [0, total).
+bool parse_erased(const int* erased, int nerased, int total, std::vector<bool>* present) {
+  present->assign(total, true);
+  for (int i = 0; i < nerased; ++i) {
+    if (erased[i] < 0 || erased[i] >= total) return false;
+    (*present)[erased[i]] = false;
+  }
+  return true;
+}
+}  // namespace
+
 Status RSEngine::encode_batch(uint8_t* const* ptrs, size_t S, int nstripes, hipStream_t stream) {
   if (!ctx_) return CFSEC_ERR_DEVICE;
   if (!ptrs || nstripes < 0) return CFSEC_ERR_INVALID_ARG;
   if (m_ == 0 || nstripes == 0 || S == 0) return CFSEC_OK;
-  std::vector<const uint8_t*> in(size_t(nstripes) * k_);
-  std::vector<uint8_t*> out(size_t(nstripes) * m_);
-  for (int s = 0; s < nstripes; ++s) {
-    for (int c = 0; c < k_; ++c) in[size_t(s) * k_ + c] = ptrs[size_t(s) * total() + c];
-    for (int r = 0; r < m_; ++r) out[size_t(s) * m_ + r] = ptrs[size_t(s) * total() + k_ + r];
-  }
+  const PtrTables t = ptr_tables(ptrs, total(), nstripes, index_range(0, k_), index_range(k_, total()));
   DeviceGuard g(ctx_->device());
   if (!g.ok()) return hip_status(hipErrorInvalidDevice, "hipSetDevice");
-  MatVecJob job;
-  job.k = k_;
-  job.m = m_;
-  job.coef = parity_.v.data();
-  job.len = S;
-  job.nstripes = nstripes;
-  job.in = in.data();
-  job.out = out.data();
+  const MatVecJob job = matvec_job(k_, m_, parity_.v.data(), S, nstripes, t.in.data(), t.out.data());
   return hip_status(launch_matvec(job, stream), "launch_matvec(encode_batch)");
 }
 
@@ -1000,23 +1005,10 @@ Status RSEngine::matvec_batch(const uint8_t* coef, int rows, uint8_t* const* ptr
   if (!ctx_) return CFSEC_ERR_DEVICE;
   if (!coef || !ptrs || nstripes < 0 || rows < 0 || rows > 256) return CFSEC_ERR_INVALID_ARG;
   if (rows == 0 || nstripes == 0 || S == 0) return CFSEC_OK;
-  const size_t w = (size_t)k_ + rows;
-  std::vector<const uint8_t*> in(size_t(nstripes) * k_);
-  std::vector<uint8_t*> out(size_t(nstripes) * rows);
-  for (int s = 0; s < nstripes; ++s) {
-    for (int c = 0; c < k_; ++c) in[size_t(s) * k_ + c] = ptrs[s * w + c];
-    for (int r = 0; r < rows; ++r) out[size_t(s) * rows + r] = ptrs[s * w + k_ + r];
-  }
+  const PtrTables t = ptr_tables(ptrs, (size_t)k_ + rows, nstripes, index_range(0, k_), index_range(k_, k_ + rows));
   DeviceGuard g(ctx_->device());
   if (!g.ok()) return hip_status(hipErrorInvalidDevice, "hipSetDevice");
-  MatVecJob job;
-  job.k = k_;
-  job.m = rows;
-  job.coef = coef;
-  job.len = S;
-  job.nstripes = nstripes;
-  job.in = in.data();
-  job.out = out.data();
+  const MatVecJob job = matvec_job(k_, rows, coef, S, nstripes, t.in.data(), t.out.data());
   return hip_status(launch_matvec(job, stream), "launch_matvec(matvec_batch)");
 }
 
@@ -1026,22 +1018,10 @@ Status RSEngine::verify_batch(uint8_t* const* ptrs, size_t S, int nstripes, uint
   if (!ptrs || !flags || nstripes < 0) return CFSEC_ERR_INVALID_ARG;
   if (m_ == 0 || nstripes == 0 || S == 0) return CFSEC_OK;
   if (k_ > 32) return CFSEC_ERR_NOT_SUPPORTED;
-  std::vector<const uint8_t*> in(size_t(nstripes) * k_);
-  std::vector<uint8_t*> out(size_t(nstripes) * m_);
-  for (int s = 0; s < nstripes; ++s) {
-    for (int c = 0; c < k_; ++c) in[size_t(s) * k_ + c] = ptrs[size_t(s) * total() + c];
-    for (int r = 0; r < m_; ++r) out[size_t(s) * m_ + r] = ptrs[size_t(s) * total() + k_ + r];
-  }
+  const PtrTables t = ptr_tables(ptrs, total(), nstripes, index_range(0, k_), index_range(k_, total()));
   DeviceGuard g(ctx_->device());
   if (!g.ok()) return hip_status(hipErrorInvalidDevice, "hipSetDevice");
-  MatVecJob job;
-  job.k = k_;
-  job.m = m_;
-  job.coef = parity_.v.data();
-  job.len = S;
-  job.nstripes = nstripes;
-  job.in = in.data();
-  job.out = out.data();
+  MatVecJob job = matvec_job(k_, m_, parity_.v.data(), S, nstripes, t.in.data(), t.out.data());
   job.mode = MatVecMode::kVerify;
   job.flags = flags;
   return hip_status(launch_matvec(job, stream), "launch_matvec(verify_batch)");
@@ -1051,11 +1031,8 @@ Status RSEngine::reconstruct_batch(uint8_t* const* ptrs, size_t S, int nstripes,
                                    int nerased, bool data_only, hipStream_t stream) {
   if (!ctx_) return CFSEC_ERR_DEVICE;
   if (!ptrs || nstripes < 0 || nerased < 0 || (nerased > 0 && !erased)) return CFSEC_ERR_INVALID_ARG;
-  std::vector<bool> present(total(), true);
-  for (int i = 0; i < nerased; ++i) {
-    if (erased[i] < 0 || erased[i] >= total()) return CFSEC_ERR_INVALID_ARG;
-    present[erased[i]] = false;
-  }
+  std::vector<bool> present;
+  if (!parse_erased(erased, nerased, total(), &present)) return CFSEC_ERR_INVALID_ARG;
   int np = 0, dp = 0;
   for (int i = 0; i < total(); ++i)
     if (present[i]) {
@@ -1067,23 +1044,11 @@ Status RSEngine::reconstruct_batch(uint8_t* const* ptrs, size_t S, int nstripes,
   ReconPlan plan;
   Status st = plan_reconstruct(present, data_only, &plan);
   if (st != CFSEC_OK) return st;
-  const int nout = (int)plan.outputs.size();
-  std::vector<const uint8_t*> in(size_t(nstripes) * k_);
-  std::vector<uint8_t*> out(size_t(nstripes) * nout);
-  for (int s = 0; s < nstripes; ++s) {
-    for (int c = 0; c < k_; ++c) in[size_t(s) * k_ + c] = ptrs[size_t(s) * total() + plan.valid[c]];
-    for (int r = 0; r < nout; ++r) out[size_t(s) * nout + r] = ptrs[size_t(s) * total() + plan.outputs[r]];
-  }
+  const PtrTables t = ptr_tables(ptrs, total(), nstripes, plan.valid, plan.outputs);
   DeviceGuard g(ctx_->device());
   if (!g.ok()) return hip_status(hipErrorInvalidDevice, "hipSetDevice");
-  MatVecJob job;
-  job.k = k_;
-  job.m = nout;
-  job.coef = plan.rows.v.data();
-  job.len = S;
-  job.nstripes = nstripes;
-  job.in = in.data();
-  job.out = out.data();
+  const int nout = (int)plan.outputs.size();
+  const MatVecJob job = matvec_job(k_, nout, plan.rows.v.data(), S, nstripes, t.in.data(), t.out.data());
   return hip_status(launch_matvec(job, stream), "launch_matvec(reconstruct_batch)");
 }
 
@@ -1124,34 +1089,17 @@ Status RSEngine::encode_crc_batch(uint8_t* const* ptrs, size_t S, int nstripes, 
     return hip_status(launch_crc32_to(p.data(), S, (int)p.size(), crcs, nullptr, crc32_shift_ones(S), stream),
                       "launch_crc32_to");
   }
-  std::vector<const uint8_t*> in(size_t(nstripes) * k_);
-  std::vector<uint8_t*> out(size_t(nstripes) * m_);
-  for (int s = 0; s < nstripes; ++s) {
-    for (int c = 0; c < k_; ++c) in[size_t(s) * k_ + c] = ptrs[size_t(s) * total() + c];
-    for (int r = 0; r < m_; ++r) out[size_t(s) * m_ + r] = ptrs[size_t(s) * total() + k_ + r];
-  }
-  MatVecJob job;
-  job.k = k_;
-  job.m = m_;
-  job.coef = parity_.v.data();
-  job.len = S;
-  job.nstripes = nstripes;
-  job.in = in.data();
-  job.out = out.data();
-  std::vector<int> slot(total());
-  for (int i = 0; i < total(); ++i) slot[i] = i;
-  return matvec_with_crc(job, ptrs, total(), slot, S, crcs, stream);
+  const PtrTables t = ptr_tables(ptrs, total(), nstripes, index_range(0, k_), index_range(k_, total()));
+  const MatVecJob job = matvec_job(k_, m_, parity_.v.data(), S, nstripes, t.in.data(), t.out.data());
+  return matvec_with_crc(job, ptrs, total(), index_range(0, total()), S, crcs, stream);
 }
 
 Status RSEngine::reconstruct_crc_batch(uint8_t* const* ptrs, size_t S, int nstripes, const int* erased,
                                        int nerased, bool data_only, uint32_t* crcs, hipStream_t stream) {
   if (!ctx_) return CFSEC_ERR_DEVICE;
   if (!ptrs || !crcs || nstripes < 0 || nerased < 0 || (nerased > 0 && !erased)) return CFSEC_ERR_INVALID_ARG;
-  std::vector<bool> present(total(), true);
-  for (int i = 0; i < nerased; ++i) {
-    if (erased[i] < 0 || erased[i] >= total()) return CFSEC_ERR_INVALID_ARG;
-    present[erased[i]] = false;
-  }
+  std::vector<bool> present;
+  if (!parse_erased(erased, nerased, total(), &present)) return CFSEC_ERR_INVALID_ARG;
   int np = 0;
   for (int i = 0; i < total(); ++i) np += present[i] ? 1 : 0;
   if (np < k_ && nstripes > 0) return CFSEC_ERR_TOO_FEW_SHARDS;
@@ -1166,20 +1114,8 @@ Status RSEngine::reconstruct_crc_batch(uint8_t* const* ptrs, size_t S, int nstri
   const int nout = (int)plan.outputs.size();
   if (nout == 0 || S == 0)
     return hip_status(hipMemsetAsync(crcs, 0, 4 * (size_t)total() * nstripes, stream), "hipMemsetAsync");
-  std::vector<const uint8_t*> in(size_t(nstripes) * k_);
-  std::vector<uint8_t*> out(size_t(nstripes) * nout);
-  for (int s = 0; s < nstripes; ++s) {
-    for (int c = 0; c < k_; ++c) in[size_t(s) * k_ + c] = ptrs[size_t(s) * total() + plan.valid[c]];
-    for (int r = 0; r < nout; ++r) out[size_t(s) * nout + r] = ptrs[size_t(s) * total() + plan.outputs[r]];
-  }
-  MatVecJob job;
-  job.k = k_;
-  job.m = nout;
-  job.coef = plan.rows.v.data();
-  job.len = S;
-  job.nstripes = nstripes;
-  job.in = in.data();
-  job.out = out.data();
+  const PtrTables t = ptr_tables(ptrs, total(), nstripes, plan.valid, plan.outputs);
+  const MatVecJob job = matvec_job(k_, nout, plan.rows.v.data(), S, nstripes, t.in.data(), t.out.data());
   std::vector<int> slot(k_ + nout, -1);
   for (int r = 0; r < nout; ++r) slot[k_ + r] = plan.outputs[r];
   return matvec_with_crc(job, ptrs, total(), slot, S, crcs, stream);

@@ -28,7 +28,6 @@ namespace cfsec {
 // synchronous calls poll a marker word (1) or hipStreamSynchronize (0): cfsec_set_sync_poll
 std::atomic<int>& sync_poll_mode();
 
-
 using Status = int;  // cfsec_status
 
 void set_last_error(const std::string& msg);
@@ -54,6 +53,17 @@ struct HostTimer {
 Status init_bad_shards(cfsec_shard* shards, int n, const std::vector<int>& bad);
 Status fill_full_shards(cfsec_shard* shards, int n);
 Status hip_status(hipError_t e, const char* what);
+// Stream `to` waits for everything queued on stream `from` so far (the two lanes of a host call).
+Status lane_wait(hipEvent_t ev, hipStream_t from, hipStream_t to);
+constexpr size_t kSlotAlign = 256;  // staging rows start on 256-B boundaries
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// KRS/reedsolomon.go:1314-1339 checkShards / shardSize.
+Status check_shards(const cfsec_shard* shards, int n, bool nilok, size_t* size);
+// The plain store of coef (m x k) over nstripes stripes of S-byte rows; callers set what else they need.
+inline MatVecJob matvec_job(int k, int m, const uint8_t* coef, size_t S, int nstripes, const uint8_t* const* in,
+                            uint8_t* const* out) {
+  return MatVecJob{k, m, coef, S, nstripes, in, out};
+}
 // The device address of page-locked host memory (hipHostMalloc / cfsec_host_alloc); false for
 // pageable memory.
 bool device_alias(uint8_t* p, uint8_t** dptr);
@@ -199,7 +209,11 @@ struct StripePlan {
   int nextra = 0;  // the last nextra rows of out are ExtraRows, compared
   Matrix rows;  // out.size() x in.size()
   std::shared_ptr<const Dy16Plan> dy16;  // set where that product is the cheaper one
+  bool compares() const { return out.size() > (size_t)nstore; }  // some row is compared (Verify)
 };
+// The plan over a whole stripe: rows (total - k x k) x shards [0, k) into shards [k, total), the first
+// nstore of them stored (an Encode: all of them), the rest compared (a Verify: nstore = 0).
+StripePlan whole_stripe_plan(int k, int total, const Matrix& rows, int nstore);
 
 // The device (0 .. ndev-1) each of n stripes of a host-memory batch runs on: contiguous runs
 // balanced by the bytes each stripe moves (cfsec_batch_partition).
@@ -236,9 +250,23 @@ struct StripeTask {
   const int* crc_map = nullptr; // shard index -> index in the item (local views), or identity
 };
 
+// The stripe ranges [t0, t1) one launch group (stripes sharing a plan) is launched in, by the
+// addresses of its rows: in[t * k + c], out[t * m + r] and (dy16 plans) hout[t * mo + r], lens[t].
+// Maximal runs of stripes at one non-zero stride from each other on every row launch as affine
+// batches; runs shorter than 4 stripes are gathered into pointer-table runs.  Groups of fewer than 3
+// stripes or of several lengths are one run.  Host arithmetic only (batch.cpp).
+std::vector<std::pair<size_t, size_t>> split_runs(const uint8_t* const* in, size_t k, const uint8_t* const* out,
+                                                  size_t m, const uint8_t* const* hout, size_t mo,
+                                                  const uint64_t* lens, size_t nt);
+// The staged tasks [i0, i1) that share one staging lane of lane_bytes, i1 returned: whole stripes,
+// every row of plan->in then plan->out (compared rows too) in a slot of align_up(len, kSlotAlign)
+// bytes; offsets gets each row's offset from the lane's base, task after task.  A task larger than
+// the lane still goes, alone.  Host arithmetic only (batch.cpp).
+size_t pack_chunk(const StripeTask* const* tasks, size_t n, size_t i0, size_t lane_bytes,
+                  std::vector<size_t>* offsets);
+
 // Plans built for one batch call (stable addresses for the tasks that point at them).
 struct PlanStore {
-  std::map<std::vector<bool>, std::unique_ptr<StripePlan>> by_pattern;
   std::vector<std::unique_ptr<StripePlan>> other;
   StripePlan* add(const StripePlan& p) {
     other.emplace_back(new StripePlan(p));
@@ -343,10 +371,8 @@ class RSEngine {
  private:
   Status run_host(const Matrix& rows, const std::vector<cfsec_shard*>& ins,
                   const std::vector<cfsec_shard*>& outs, size_t S, MatVecMode mode, bool* ok);
-
- public:
-
- private:
+  // encode_stripes (nstore = m) and verify_stripes (nstore = 0): the parity rows over whole stripes
+  Status whole_stripes(cfsec_shard* const* stripes, int nst, int mem, int* status, int nstore);
   RSEngine() = default;
   int k_ = 0, m_ = 0;
   Matrix mat_;     // total x k
