@@ -556,10 +556,6 @@ hipError_t plan_dy16_repair(const Dy16RepairJob& job, RepairVisitor visit, void*
   const bool net = job.syn && kBs16 && nd <= kBsRepairMaxNd && !job.lens && job.len >= kBs16Tile &&
                    bs_matches(job.coef, 20 + ne, 16);
   const uint64_t full = net ? job.len / kBs16Tile * kBs16Tile : 0;
-  // ... with the stored rows' checksums in that pass when it covers the whole row: the missing data
-  // rows then the stored parity rows, at most 4 (gf_bs16.hip's checksummed rows)
-  const int ncrc = nd + __builtin_popcount(job.pstore);
-  const int crc_rows = net && full == job.len && job.crc_words && job.crc_done && ncrc >= 1 && ncrc <= 4 ? ncrc : 0;
   // Stripes at unrelated addresses (every shard its own buffer, as blobnode assembles a bid): the
   // bit-sliced repair over a table of 32-bit row offsets, every stripe in one step
   uint64_t off = 0;
@@ -569,7 +565,6 @@ hipError_t plan_dy16_repair(const Dy16RepairJob& job, RepairVisitor visit, void*
     t.ns = job.nstripes;
     t.bs = RepairBs::kTable;
     t.prefix = full;
-    t.crc_rows = crc_rows;
     t.rows = tl_rows.data();
     const hipError_t e = visit(t, ctx);
     if (e != hipSuccess) return e;
@@ -586,7 +581,6 @@ hipError_t plan_dy16_repair(const Dy16RepairJob& job, RepairVisitor visit, void*
     st.bs = affine ? RepairBs::kAffine : RepairBs::kNone;
     st.off = off;
     st.prefix = affine ? full : 0;
-    st.crc_rows = affine ? crc_rows : 0;
     st.tail = llen - off - st.prefix;
     const hipError_t e = visit(st, ctx);
     if (e != hipSuccess) return e;
@@ -608,11 +602,10 @@ hipError_t dispatch_repair(RepairStep& st, void* ctx) {
   const Dy16RepairJob& job = d.job;
   GfArgs& a = d.a;
   const int nd = job.nd, ne = job.e, mo = nd + 20 + ne, ns = st.ns;
-  const bool crc = st.crc_rows > 0;
   if (d.trace)
-    std::fprintf(stderr, "cfsec: repair bs=%s crc=%d nd=%d e=%d s0=%d stripes=%d prefix=%llu tail=%llu affine=%d\n",
-                 st.bs == RepairBs::kTable ? "table" : st.bs == RepairBs::kAffine ? "affine" : "none", crc, nd, ne,
-                 st.s0, ns, (unsigned long long)st.prefix, (unsigned long long)st.tail, st.sstride != 0);
+    std::fprintf(stderr, "cfsec: repair bs=%s nd=%d e=%d s0=%d stripes=%d prefix=%llu tail=%llu affine=%d\n",
+                 st.bs == RepairBs::kTable ? "table" : st.bs == RepairBs::kAffine ? "affine" : "none", nd, ne, st.s0,
+                 ns, (unsigned long long)st.prefix, (unsigned long long)st.tail, st.sstride != 0);
   if (d.first) {  // what every launch of the (validated) job shares
     d.first = false;
     a.k = 16;
@@ -639,25 +632,12 @@ hipError_t dispatch_repair(RepairStep& st, void* ctx) {
   if (st.bs != RepairBs::kNone) {
     uint8_t missing[4];
     missing_rows(job.src, missing);
-    BsCrcReq req;
-    if (crc) {  // the words are zeroed by the caller: no in-kernel zeroing to race the atomics
-      req.nrows = st.crc_rows;
-      req.stride = job.crc_stride;
-      req.mode = job.crc_mode;
-      for (int q = 0; q < 4; ++q) req.slot[q] = job.crc_slot[q];
-      a.zw = nullptr;
-      a.nzw = 0;
-    }
-    uint32_t* words = crc ? job.crc_words + (size_t)st.s0 * job.crc_stride : nullptr;
-    bool fused = false, ok = true;  // (ok: the 4 GiB span, which the plan has checked)
+    bool ok = true;  // (the 4 GiB span, which the plan has checked)
     e = st.bs == RepairBs::kTable
             ? launch_bs16_repair_tab(nd, ne, missing, job.prow, job.ainv, a, st.rows, (unsigned)ns, st.prefix,
-                                     d.stream, &ok, crc ? &req : nullptr, words, &fused)
-            : launch_bs16_repair(nd, ne, missing, job.prow, job.ainv, a, (unsigned)ns, st.prefix, d.stream,
-                                 crc ? &req : nullptr, words, &fused);
+                                     d.stream, &ok)
+            : launch_bs16_repair(nd, ne, missing, job.prow, job.ainv, a, (unsigned)ns, st.prefix, d.stream);
     if (e == hipSuccess && !ok) e = hipErrorInvalidValue;  // (not reached: rows_fit_bs has used the launcher's span test)
-    if (fused)
-      for (int s = 0; s < ns; ++s) job.crc_done[st.s0 + s] = 1;
   }
   if (e == hipSuccess && st.tail) {
     if (st.off + st.prefix) skip_prefix(a, st.off + st.prefix);

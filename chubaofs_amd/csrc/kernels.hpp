@@ -56,21 +56,8 @@ struct Dy16RepairJob {
   bool syn = false;                    // the syndrome form below is set: the bit-sliced kernel may run
   uint8_t prow[4] = {};                // input 16 - nd + q is parity row prow[q]
   uint8_t ainv[16] = {};               // missing row j = sum_q ainv[j * 4 + q] * syndrome of prow[q]
-  // the stored rows' checksums in the same pass (bit-sliced kernel only): stripe s's checksummed row
-  // k (the missing data rows, then the stored parity rows in order) XOR-accumulates crc32.ChecksumIEEE
-  // into crc_words[s * crc_stride + crc_slot[k]] (zeroed by the caller, zero_words must be NULL);
-  // crc_done[s] is set to 1 for the stripes whose words the launches accumulated (host array)
-  uint32_t* crc_words = nullptr;
-  uint32_t crc_stride = 0;
-  uint8_t crc_slot[4] = {};
-  int crc_mode = 1;  // gf_launch.hpp BsCrcReq::mode
-  char* crc_done = nullptr;
 };
 hipError_t launch_dy16_repair(const Dy16RepairJob& job, hipStream_t stream);
-// what the bit-sliced repair (and its checksums) takes: whole 2 KiB column tiles, <= 2 missing data
-// rows (gf_launch.hpp kBs16Tile / kBsRepairMaxNd)
-constexpr uint64_t kBsRepairTileBytes = 2048;
-constexpr int kBsRepairMaxMissing = 2;
 
 // Verify flags of a batch call gathered per batch item (batch.cpp run_device): for every item o,
 // out[o] = OR of the per-task words tmp[word[j]] of the pairs (o, word[j]) -- `accumulate`: out[o] |=
@@ -130,12 +117,11 @@ const char* bs_prefix_name(BsPrefix p);          // "none", "encode", "verify", 
 // prefix=.. tail=.. affine=..".
 
 // launch_dy16_repair's decisions, the same way: per job the table launch, per run the affine
-// bit-sliced prefix, whether the checksums ride in that pass, and the dyadic tail.
+// bit-sliced prefix and the dyadic tail.
 enum class RepairBs : int { kNone = 0, kAffine, kTable };
 struct RepairStep {
   int s0, ns;
   RepairBs bs;  // kTable: every stripe at once (s0 = 0), the runs after it carry off = prefix
-  int crc_rows;  // > 0: that many stored rows' checksums ride in this step's bit-sliced pass (whole rows)
   uint64_t off, prefix, tail;
   int64_t sstride;
   const uint8_t* const* rows;  // kTable: as MatVecStep::rows (this table launch has no runtime fallback)

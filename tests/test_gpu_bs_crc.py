@@ -1,17 +1,15 @@
-"""The rebuilt shards' checksums computed inside the bit-sliced repair pass (round 5).
+"""The rebuilt shards' checksums of the 16 + 20 code's repair (the bit-sliced repair kernel, then
+the separate checksum pass).
 
 Blobnode checksums every shard a repair rebuilds (work_shard_recover.go:335-342, ShardCrc32); the
-C5 tasklet (EC16P20L2, erased {0, 1, 16, 17}) used to take a second pass over the 256 rebuilt rows.
-gf_bs16.hip's CRC launches fold crc32.ChecksumIEEE of the stored rows into the repair pass itself
-(batch.cpp dy16_crc_group).  Every case here compares statuses, every shard and the words with the
-ec oracle's repair and zlib; CFSEC_TRACE_BATCH names which groups the repair pass checksummed, so
-the routing (fused: whole 2 KiB tiles, <= 4 stored rows, 0 or 2 missing data rows; else the
-separate pass) is pinned too.  The route is off by default, so these tests turn it on: mode 1 (the
-Horner steps inside the network, measured slower than the separate pass) and mode 2
-(round 6: each wave checksums the rows of its own tiles after its last tile).
+C5 tasklet (EC16P20L2, erased {0, 1, 16, 17}) takes a second pass over the 256 rebuilt rows after
+gf_bs16.hip's repair launch.  (Two forms that folded crc32.ChecksumIEEE into the repair pass itself
+were measured slower and removed)  Every case here compares statuses, every shard
+and the words with the ec oracle's repair and zlib: one slab at a bid stride and every shard at its
+own address, 0, 1 and 2 missing data rows, four and five rebuilt rows, corrupted bids, C5's own
+shape through the asynchronous call, and a row tail.
 """
 import random
-import re
 import zlib
 
 import numpy as np
@@ -47,14 +45,8 @@ def oracle_repair(shards, bad):
     return st, [w.view().copy() for w in work]
 
 
-def fused_counts(err):
-    return [(int(a), int(b)) for a, b in re.findall(r"repair-pass crc group tasks=(\d+) fused=(\d+)", err)]
-
-
-def test_repair_pass_checksums_off_by_default(monkeypatch, capfd):
-    """Without CFSEC_BS_REPAIR_CRC the rebuilt shards' checksums take the separate pass."""
-    monkeypatch.setenv("CFSEC_TRACE_BATCH", "1")
-    monkeypatch.delenv("CFSEC_BS_REPAIR_CRC", raising=False)
+def test_repair_pass_checksums_one_bid():
+    """One bid of one 2 KiB tile: the rebuilt shards' words equal zlib's, every other word stays 0."""
     enc = enc_new()
     t = cm.GetTactic(MODE)
     n = t.N + t.M + t.L
@@ -62,23 +54,17 @@ def test_repair_pass_checksums_off_by_default(monkeypatch, capfd):
     good = codeword(S, 5)
     views = [torch.from_numpy(x.copy() if i not in bad else np.zeros(S, np.uint8)).cuda() for i, x in enumerate(good)]
     st, crcs = enc.ReconstructBatch([views], [bad], crcs=True)
-    assert st == [0] and "repair-pass crc group" not in capfd.readouterr().err
+    assert st == [0]
     assert [crcs[0][i] for i in bad] == [zlib.crc32(good[i].tobytes()) for i in bad]
     assert [crcs[0][i] for i in range(n) if i not in bad] == [0] * (n - len(bad))
 
 
-@pytest.mark.parametrize("mode", ["1", "2"])
 @pytest.mark.parametrize("layout", ["slab", "scattered"])
-@pytest.mark.parametrize("bad,fused", [([0, 1, 16, 17], True), ([16, 17], True), ([5, 12, 30], True),
-                                       ([3, 20], False), ([0, 1, 16, 17, 18], False)])
-def test_repair_pass_checksums(mode, layout, bad, fused, monkeypatch, capfd):
+@pytest.mark.parametrize("bad", [[0, 1, 16, 17], [16, 17], [5, 12, 30], [3, 20], [0, 1, 16, 17, 18]])
+def test_repair_pass_checksums(layout, bad):
     """24 bids of one erasure pattern at S = 3 x 2 KiB: one slab at a bid stride (one affine launch)
     or every shard at its own address (the device row-offset table); bids 4 and 17 carry a corrupted
-    compared parity (ErrVerify; their words are 0, clear_failed_crcs).  ([3, 20]: one missing data row
-    -- no mode-1 form, the separate pass; mode 2 takes it.  Five rows rebuilt -- more than the kernel's 4.)"""
-    monkeypatch.setenv("CFSEC_TRACE_BATCH", "1")
-    monkeypatch.setenv("CFSEC_BS_REPAIR_CRC", mode)
-    fused = fused or (mode == "2" and bad == [3, 20])
+    compared parity (ErrVerify; their words are 0, clear_failed_crcs)."""
     enc = enc_new()
     t = cm.GetTactic(MODE)
     n = t.N + t.M + t.L
@@ -105,7 +91,6 @@ def test_repair_pass_checksums(mode, layout, bad, fused, monkeypatch, capfd):
         for i in range(n):
             views[b][i].copy_(torch.from_numpy(srcs[b][i] if i not in bad else np.zeros(S, np.uint8)))
     st, crcs = enc.ReconstructBatch(views, [bad] * nb, crcs=True)
-    err = capfd.readouterr().err
     assert st == [w[0] for w in want]
     assert st[4] == _lib.ErrVerify.status and st[17] == _lib.ErrVerify.status
     for b, (exp, shards) in enumerate(want):
@@ -113,19 +98,12 @@ def test_repair_pass_checksums(mode, layout, bad, fused, monkeypatch, capfd):
             assert np.array_equal(views[b][i].cpu().numpy(), shards[i]), (b, i)
             w = zlib.crc32(shards[i].tobytes()) if exp == 0 and i in bad else 0
             assert crcs[b][i] == w, (layout, bad, b, i, hex(crcs[b][i]), hex(w))
-    counts = fused_counts(err)
-    if fused:
-        assert counts and sum(f for _, f in counts) == nb, err
-    else:
-        assert sum(f for _, f in counts) == 0, err
 
 
-@pytest.mark.parametrize("mode", ["1", "2"])
-def test_repair_pass_checksums_c5_async_and_tail(mode, monkeypatch):
+def test_repair_pass_checksums_c5_async_and_tail():
     """C5's tasklet (64 bids x 262,144 B) through the asynchronous call with device words -- every
     rebuilt shard's word equals zlib's, the Verify flags of the two corrupted bids set -- and the same
-    tasklet at S = 262,144 + 48 (a row tail: the separate pass), equal words."""
-    monkeypatch.setenv("CFSEC_BS_REPAIR_CRC", mode)
+    tasklet at S = 262,144 + 48 (a row tail: the dyadic kernel finishes each row), equal words."""
     enc = enc_new()
     t = cm.GetTactic(MODE)
     n = t.N + t.M + t.L

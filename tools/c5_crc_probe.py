@@ -1,7 +1,6 @@
 """C5's tasklet (EC16P20L2, 64 bids x S = 262,144, erased {0, 1, 16, 17}) through
 cfsec_ec_reconstruct_batch_async with and without the rebuilt shards' checksums: device time per
-call from HIP events (back-to-back calls), every bid's words against zlib (CFSEC_BS_REPAIR_CRC=1 / 2:
-the repair-pass checksum forms).  Run under
+call from HIP events (back-to-back calls), every bid's words against zlib.  Run under
 rocprofv3 --kernel-trace --stats to see the launches one call makes."""
 import ctypes
 import os
