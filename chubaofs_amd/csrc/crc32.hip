@@ -6,9 +6,11 @@
 // Same algebra and work split as the fused kernel, without the product: a workgroup owns `tpw`
 // consecutive 4 KiB tiles of one shard, thread j a 16-byte piece of each (coalesced 16-B loads,
 // the next tile's piece in flight while this one is folded), Horner R <- f(shift(R, 4080), piece)
-// with the conflict-free nibble tables (gf_crc.hpp crc_step_nib), a per-thread basis multiply to the tile end, a workgroup XOR
-// reduction and one multiply by x^(8(S - e)) to the shard end, then atomicXor into the shard's
-// word.  `fin` (crc32_shift_ones(S), or 0 for the raw word) is folded in by workgroup 0.
+// with the conflict-free 5-bit tables (gf_crc.hpp crc_step5: 35 reads per piece; the nibble and byte
+// table steps it replaced: profiles/r02/crc_only_step_ab.txt), a per-thread basis multiply to the
+// tile end, a workgroup XOR reduction and one multiply by x^(8(S - e)) to the shard end, then
+// atomicXor into the shard's word.  `fin` (crc32_shift_ones(S), or 0 for the raw word) is folded in
+// by workgroup 0.
 #include <algorithm>
 #include <cstdlib>
 #include <vector>
@@ -19,9 +21,7 @@
 namespace cfsec {
 namespace {
 
-using crcdev::kBasisWords;
 using crcdev::kMaxGroups;
-using crcdev::kTabWords;
 using crcdev::kTile;
 using dev::u32x4;
 // Argument block: the fixed fields, then a flexible area of words holding the group constants
@@ -73,9 +73,9 @@ __device__ __forceinline__ void piece(const uint8_t* p, uint64_t len, uint32_t o
 #endif
 __global__ __launch_bounds__(256) void crc32_horner_kernel(const CrcArgs a) {
   constexpr int A = CFSEC_CRC_AHEAD;
-  __shared__ uint32_t ct[crcdev::kOnlyTabWords];
+  __shared__ uint32_t ct[crcdev::kFiveTabWords];
   __shared__ uint32_t red[4];
-  for (int i = threadIdx.x; i < crcdev::kOnlyTabWords; i += 256) ct[i] = a.tabs[crcdev::kOnlyTabBase + i];
+  for (int i = threadIdx.x; i < crcdev::kFiveTabWords; i += 256) ct[i] = a.tabs[crcdev::kFiveTabBase + i];
   __syncthreads();
   const uint32_t g = blockIdx.x, sh = blockIdx.y;
   const uint8_t* p = a.sstride ? shard_ptr(a, 0) + (int64_t)sh * a.sstride : shard_ptr(a, sh);
@@ -93,11 +93,11 @@ __global__ __launch_bounds__(256) void crc32_horner_kernel(const CrcArgs a) {
 #if CFSEC_CRC_DIAG == 2
         R = (R << 1 | R >> 31) ^ buf[k][0] ^ buf[k][1] ^ buf[k][2] ^ buf[k][3];
 #else
-        R = crcdev::only_step(ct, R, buf[k]);
+        R = crcdev::crc_step5(ct, R, buf[k]);
 #endif
       }
   }
-  const u32x4* basis = reinterpret_cast<const u32x4*>(a.tabs + kTabWords + threadIdx.x * 32);
+  const u32x4* basis = reinterpret_cast<const u32x4*>(a.tabs + crcdev::kBasisBase + threadIdx.x * 32);
   uint32_t o = 0;
 #if CFSEC_CRC_DIAG == 1
   o = R;

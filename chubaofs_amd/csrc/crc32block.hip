@@ -11,8 +11,8 @@
 // owns block b0 + w of object y, streams its payload in 4 KiB tiles cut at 16-byte boundaries of
 // the destination (thread j: the 16-byte piece j of each tile, the next tile's piece in flight;
 // loads may be unaligned, stores are aligned), folds every
-// piece into a Horner register with the nibble LDS tables of the shard CRC kernels (gf_crc.hpp
-// crc_step_nib: R <- f(shift(R, 4080), piece)), and copies the piece to its destination.  After the last tile a
+// piece into a Horner register with the 5-bit LDS tables of the shard CRC kernels (gf_crc.hpp
+// crc_step5: R <- f(shift(R, 4080), piece)), and copies the piece to its destination.  After the last tile a
 // per-thread basis moves R to the tile end, the workgroup XOR-reduces, and one multiply by
 // x^(8(plen - tiles*4096)) (a negative power: the zero padding of the last tile) gives the raw
 // (zero-preset) CRC of the payload; XOR-ing shift(~0, plen) ^ ~0 makes it ChecksumIEEE.  Encode
@@ -30,7 +30,6 @@
 namespace cfsec {
 namespace blk {
 
-using crcdev::kTabWords;
 using crcdev::kTile;
 using dev::u32x4;
 
@@ -92,13 +91,13 @@ __device__ __forceinline__ void load_piece(const uint8_t* src, uint32_t plen, ui
 // runs STORE, CRC and EPI on, pieces aligned to the destination).
 template <bool STORE = true, bool CRC = true, bool EPI = true, bool SRCALIGN = false, bool NTS = true>
 __global__ __launch_bounds__(256) void crc32block_kernel(const BlockArgs a) {
-  __shared__ uint32_t ct[crcdev::kOnlyTabWords];
+  __shared__ uint32_t ct[crcdev::kFiveTabWords];
   __shared__ uint32_t red[4];
-  for (int i = threadIdx.x; i < crcdev::kOnlyTabWords; i += 256) ct[i] = a.tabs[crcdev::kOnlyTabBase + i];
+  for (int i = threadIdx.x; i < crcdev::kFiveTabWords; i += 256) ct[i] = a.tabs[crcdev::kFiveTabBase + i];
   // this thread's x^(8*16*(255 - j)): moves its Horner register from its piece to the tile end
   // (gf_crc.hip host_tables; one coalesced word per thread -- reading column x^0 of the
   // per-thread basis instead, 128 B apart, cost one L2 request per thread per block)
-  const uint32_t kj = a.tabs[kTabWords + crcdev::kBasisWords + threadIdx.x];
+  const uint32_t kj = a.tabs[crcdev::kShiftBase + threadIdx.x];
   __syncthreads();
   // work items (launch block w, object y), y-major; a workgroup takes a run of consecutive ones,
   // so the table load above is paid once per workgroup and the whole-object checksum is a Horner
@@ -152,7 +151,7 @@ __global__ __launch_bounds__(256) void crc32block_kernel(const BlockArgs a) {
         if (t < tiles) {
           uint32_t (&cur)[4] = ring[k];
           const uint32_t p = t * 256 + threadIdx.x;
-          if constexpr (CRC) R = crcdev::only_step(ct, R, cur);
+          if constexpr (CRC) R = crcdev::crc_step5(ct, R, cur);
           else R ^= cur[0] ^ cur[1] ^ cur[2] ^ cur[3];
           const int64_t first = (int64_t)16 * p - h;
           if (STORE && first < (int64_t)plen) {
@@ -210,11 +209,11 @@ __global__ __launch_bounds__(256) void crc32block_kernel(const BlockArgs a) {
 // thread 0 only XORs four words and stores or compares the header.
 template <int RING, bool NTS = true, bool STRIDE = false>
 __global__ __launch_bounds__(256) void crc32block_block_kernel(const BlockArgs a) {
-  __shared__ uint32_t ct[crcdev::kOnlyTabWords];
+  __shared__ uint32_t ct[crcdev::kFiveTabWords];
   __shared__ uint32_t redb[2][8];  // per wave: its share of the block's raw CRC, and of the object's
-  for (int i = threadIdx.x; i < crcdev::kOnlyTabWords; i += 256) ct[i] = a.tabs[crcdev::kOnlyTabBase + i];
+  for (int i = threadIdx.x; i < crcdev::kFiveTabWords; i += 256) ct[i] = a.tabs[crcdev::kFiveTabBase + i];
   const uint32_t tid = threadIdx.x;
-  const uint32_t kj = a.tabs[kTabWords + crcdev::kBasisWords + tid];
+  const uint32_t kj = a.tabs[crcdev::kShiftBase + tid];
   __syncthreads();
   uint32_t it = blockIdx.x;
   if (it >= a.items) return;  // whole workgroup: no barrier follows
@@ -281,7 +280,7 @@ __global__ __launch_bounds__(256) void crc32block_block_kernel(const BlockArgs a
     // piece t*256 + tid: Horner step, then the copy to the destination
     const auto piece = [&](uint32_t t, uint32_t (&pc)[4]) {
       const uint32_t p = t * 256 + tid;
-      R = crcdev::only_step(ct, R, pc);
+      R = crcdev::crc_step5(ct, R, pc);
       const int64_t first = (int64_t)16 * p - cur.h;
       if (first + 16 > (int64_t)cur.sbeg && first < (int64_t)cur.lim) {  // sbeg > 0 is a piece boundary
         const int64_t q = (int64_t)cur.q0 + first;
@@ -340,7 +339,7 @@ __global__ __launch_bounds__(256) void crc32block_block_kernel(const BlockArgs a
       // this wave's share of the block's raw CRC: x^(8(plen + h - tiles*4096)) from the host's
       // factor for h mod 16 and x^(8*16*(h >> 4)), a word of the per-thread shift table
       const uint32_t b16 = cur.h & 15u, dt = cur.tiles - ((cur.plen + b16 + kTile - 1) / kTile);
-      const uint32_t g = crcdev::mulmod(a.gc4k[cur.last][b16][dt], a.tabs[kTabWords + crcdev::kBasisWords + 255 - (cur.h >> 4)]);
+      const uint32_t g = crcdev::mulmod(a.gc4k[cur.last][b16][dt], a.tabs[crcdev::kShiftBase + 255 - (cur.h >> 4)]);
       const uint32_t raw = crcdev::mulmod(g, v);
       red[tid >> 6] = raw;
       if (a.encode && a.whole) {

@@ -1,6 +1,8 @@
-// gf_bs_crc.hip -- fused encode + crc32.ChecksumIEEE of every shard on the bit-sliced networks
-// (round 6): EC6P10L2's fused LRC encode with all 18 checksums (C4's put; access checksums every shard
-// right after Encode, blobstore/access/stream_put.go:249-253) and EC12P4's encode with its 16.
+// gf_bs_crc.hip -- fused encode + crc32.ChecksumIEEE of every shard on the bit-sliced networks: every
+// code mode's encode or fused LRC encode (the table kBcNets below; first EC6P10L2's with all 18
+// checksums, C4's put -- access checksums every shard right after Encode,
+// blobstore/access/stream_put.go:249-253), and the product alone for the two widest LRC modes.
+// One kernel template, one launch geometry (plan_bs_crc, a host function tests/test_crc_plan.py pins).
 //
 // The lookup-product kernel (gf_crc.hpp gf_crc_lds_kernel) gets the products and the input rows'
 // checksums from one LDS read per nibble but pays a second round of lookups for every output row's
@@ -67,12 +69,10 @@
 #include "bs_net_ec16p20l2.hpp"
 #include "bs_net_ec6p10l2.hpp"
 #include "gf_bitslice.hpp"
+#include "gf_crc.hpp"
 #include "gf_launch.hpp"
 
 namespace cfsec {
-
-uint32_t crc_xpow(int64_t e);                 // gf_crc.hip: x^e mod P (e < 0: powers of x^-1)
-uint32_t crc_mulmod(uint32_t a, uint32_t b);  // a * b mod P (reflected)
 
 namespace {
 
@@ -85,7 +85,6 @@ constexpr int kBcJump = kBcPlaneTabs;             // 7 tables: the register move
 constexpr int kBcTree = kBcJump + kBcFields;       // the lane tree's 6 levels: shift by 16 * 2^k bytes
 constexpr int kBcTabs = kBcTree + 6 * kBcFields;   // 105 x 32 words
 constexpr int kBcPow = 64;        // tile-power tables: x^(8 * 2048 * i * 64^d) for d = 0, 1, 2
-constexpr uint32_t kBcPoly = 0xEDB88320u;
 constexpr uint64_t kBcTile = 2048;
 
 struct __attribute__((aligned(16))) BcArgs {
@@ -93,8 +92,8 @@ struct __attribute__((aligned(16))) BcArgs {
   int64_t sstride;       // affine batch: stripe s's row i at ptr[i] + s * sstride (0: explicit table)
   uint32_t tps, ntiles;  // 2 KiB column tiles per stripe (the last one may be partial), in the launch
   uint32_t tab, crc_stride;
-  uint32_t nst, wps, groups;  // the per-row form: stripes, waves per stripe W, wave groups (<= nst)
-  uint32_t xjump;             // the per-row form: x^(8 * 2048 * W)
+  uint32_t nst, wps, groups;  // stripes, waves per stripe W, wave groups (<= nst)
+  uint32_t xjump;             // x^(8 * 2048 * W)
   uint32_t fin;               // shift(~0, len) ^ ~0
   uint32_t bend;              // tiles [0, bend) of a stripe go round the W waves (bend = W floor(tps / W))
   uint32_t tail, tblk;        // the stripes' last tps - bend tiles: one per wave of workgroups >= tblk
@@ -109,60 +108,44 @@ struct __attribute__((aligned(16))) BcArgs {
 };
 static_assert(sizeof(BcArgs) <= 3584, "kernel argument block below 4 KiB");
 
-__device__ __forceinline__ uint32_t bc_x3(uint32_t a, uint32_t b, uint32_t c) {
-  return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
-}
+using crcdev::five7;  // XOR of the 7 lookups of a word's 5-bit fields in the tables at tb[f * 32]
 
-// XOR of the 7 lookups of word v's 5-bit fields in tables tb[f * 32] (gf_crc.hpp five_word's masked
-// copies: each v_bfe_u32 yields the byte offset 4 * field)
-__device__ __forceinline__ uint32_t bc_five7(const uint32_t* tb, uint32_t v) {
-  uint32_t e = v & 0xC1F07C00u, o = v & 0x3E0F83E0u;
-  asm volatile("" : "+v"(e), "+v"(o));
-  const uint32_t off[7] = {(v << 2) & 0x7Cu,           __builtin_amdgcn_ubfe(o, 3, 7),  __builtin_amdgcn_ubfe(e, 8, 7),
-                           __builtin_amdgcn_ubfe(o, 13, 7), __builtin_amdgcn_ubfe(e, 18, 7), __builtin_amdgcn_ubfe(o, 23, 7),
-                           __builtin_amdgcn_ubfe(e, 28, 4)};
-  uint32_t t[7];
-#pragma unroll
-  for (int f = 0; f < 7; ++f)
-    t[f] = *reinterpret_cast<const uint32_t*>(reinterpret_cast<const uint8_t*>(tb + f * 32) + off[f]);
-  return bc_x3(bc_x3(t[0], t[1], t[2]), bc_x3(t[3], t[4], t[5]), t[6]);
-}
-
-#ifndef CFSEC_BC_LO
-#define CFSEC_BC_LO 1  // the 16 + 20 code's output rows' registers in LDS too (A/B)
-#endif
-#ifndef CFSEC_BC_WPE
-#define CFSEC_BC_WPE 3  // waves per SIMD the per-row form is compiled for
-#endif
+// Timing probes only (wrong words), the cost split DESIGN §7 cites: bit 0 no input-row terms, bit 1
+// no output-row terms, bit 2 no register jumps.  Read by bc_jump and bc_take below, nowhere else.
 #ifndef CFSEC_BC_PROBE
-#define CFSEC_BC_PROBE 0  // timing probes only (wrong words): bit 0 no input-row terms, bit 1 no output-row terms,
-                          // bit 2 no register jumps
+#define CFSEC_BC_PROBE 0
 #endif
 
-// The lane's term of a row from its 8 planes p: 56 lookups, BC_PL planes' worth in flight at a time
-#ifndef CFSEC_BC_PL
-#define CFSEC_BC_PL 2
-#endif
+// The lane's term of a row from its 8 planes p: 56 lookups, 2 planes' worth in flight at a time
 __device__ __forceinline__ uint32_t bc_planes(const uint32_t* tb, const uint32_t (&p)[8]) {
   uint32_t u = 0;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
-    u ^= bc_five7(tb + j * kBcFields * 32, p[j]);
+    u ^= five7(tb + j * kBcFields * 32, p[j]);
     asm volatile("" : "+v"(u));  // XOR-ed here: sunk to the row's next use, the lookups' words stay live (spills)
-    if ((j + 1) % CFSEC_BC_PL == 0) __builtin_amdgcn_sched_barrier(0);
+    if (j % 2 == 1) __builtin_amdgcn_sched_barrier(0);
   }
   return u;
 }
 
-// a * b mod P (reflected: bit 31 = x^0)
-__device__ __forceinline__ uint32_t bc_mulmod(uint32_t a, uint32_t b) {
-  uint32_t p = 0;
-#pragma unroll
-  for (int i = 31; i >= 0; --i) {
-    p ^= (a >> i & 1u) ? b : 0u;
-    b = (b >> 1) ^ ((b & 1u) ? kBcPoly : 0u);
+// A Horner register moved on by the launch's tile stride (the jump tables at tb)
+__device__ __forceinline__ uint32_t bc_jump(const uint32_t* tb, uint32_t r) {
+  return (CFSEC_BC_PROBE & 4) ? r : five7(tb + kBcJump * 32, r);
+}
+// Row i's register takes this tile's term (planes p; OUT: an output row).  reg is the register itself
+// (VGPR-resident: jumped between tiles, in the tile loop) or its LDS word (LDS: read, jumped unless
+// this is the wave's first tile of the stripe, and written back here).
+template <bool LDS, bool OUT>
+__device__ __forceinline__ void bc_take(const uint32_t* tb, uint32_t* reg, bool fresh, const uint32_t (&p)[8]) {
+  constexpr bool kTerm = !(CFSEC_BC_PROBE & (OUT ? 2 : 1));
+  if constexpr (LDS) {
+    uint32_t v = fresh ? 0u : bc_jump(tb, *reg);
+    if constexpr (kTerm) v ^= bc_planes(tb, p);
+    *reg = v;
+  } else {
+    if constexpr (kTerm) *reg ^= bc_planes(tb, p);
+    asm volatile("" : "+v"(*reg));
   }
-  return p;
 }
 
 // A lane's 16 bytes of a row at byte po: whole, the row's last partial piece, or past the end (zeros)
@@ -180,17 +163,13 @@ __device__ __forceinline__ void bc_st(uint8_t* row, uint64_t po, uint64_t len, u
 // the fixed-K kernels' 12 outputs and ran as two products)
 template <class Net, int M, bool CRC = true>
 __global__ __launch_bounds__(64 * kBcWaves) __attribute__((amdgpu_waves_per_eu(
-    Net::K > 12 || (Net::K > 8 && M > 4) || M > 12 ? 2 : CFSEC_BC_WPE, 4))) void gf_bs_crc_kernel(const BcArgs a) {
+    Net::K > 12 || (Net::K > 8 && M > 4) || M > 12 ? 2 : 3, 4))) void gf_bs_crc_kernel(const BcArgs a) {
   constexpr int K = Net::K;
   constexpr int NR = K + M;  // checksummed rows: the inputs, then the outputs
   static_assert(NR <= 64, "one lane per row's word");
   // the rows padded for the lane fold: log2(NP) halving levels then 6 - log2(NP) lane butterflies, NP -
   // 1 + 6 - log2(NP) register-steps (8 rows: 10 instead of the 32 a 32-row padding took)
-#ifndef CFSEC_BC_NPMIN
-#define CFSEC_BC_NPMIN 8
-#endif
-  constexpr int NP = NR <= CFSEC_BC_NPMIN ? CFSEC_BC_NPMIN : NR <= 16 ? (16 > CFSEC_BC_NPMIN ? 16 : CFSEC_BC_NPMIN)
-                     : NR <= 32 ? 32 : 64;
+  constexpr int NP = NR <= 8 ? 8 : NR <= 16 ? 16 : NR <= 32 ? 32 : 64;
   constexpr int LG = NP == 8 ? 3 : NP == 16 ? 4 : NP == 32 ? 5 : 6;
   __shared__ uint32_t tb[CRC ? kBcTabs * 32 : 1];  // planes, the jump, the lane tree
   __shared__ uint32_t slot[64];  // the rows' word offsets, indexed per lane at the segment ends
@@ -198,9 +177,9 @@ __global__ __launch_bounds__(64 * kBcWaves) __attribute__((amdgpu_waves_per_eu(
   // live in LDS across the network -- read, jumped and updated at each tile's input phase -- instead of
   // in VGPRs the network needs (79 spilled at 2 waves per SIMD otherwise)
   constexpr bool LI = CRC && K > 8;
-  // LO (k > 12 or m > 12: the 16 + 20 code, EC6P6L9, EC6P8L10): the output rows' registers too, read, jumped and updated where the
-  // network emits each row
-  constexpr bool LO = CRC && (K > 12 || M > 12) && CFSEC_BC_LO;
+  // LO (k > 12 or m > 12: the 16 + 20 code, EC6P6L9, EC6P8L10): the output rows' registers too, read,
+  // jumped and updated where the network emits each row
+  constexpr bool LO = CRC && (K > 12 || M > 12);
   constexpr int NL = (LI ? K : 0) + (LO ? M : 0);  // rows whose registers live in LDS
   // row i's LDS slot (in_lds(i)): the inputs first when LI, then the outputs when LO
   const auto in_lds = [](int i) { return (LI && i < K) || (LO && i >= K); };
@@ -214,7 +193,7 @@ __global__ __launch_bounds__(64 * kBcWaves) __attribute__((amdgpu_waves_per_eu(
     // the register's jump over the launch's tile stride (2048 W bytes): table (kBcJump + f)[e] =
     // shift(e << 5f, 2048 W), built here from x^(8 * 2048 * W)
     for (uint32_t i = threadIdx.x; i < kBcFields * 32; i += blockDim.x)
-      tb[kBcJump * 32 + i] = bc_mulmod((i & 31u) << (5 * (i >> 5)), a.xjump);
+      tb[kBcJump * 32 + i] = crcdev::mulmod((i & 31u) << (5 * (i >> 5)), a.xjump);
     if (threadIdx.x == 0)  // constant indices: a lane-indexed read of the argument block would copy it to scratch
 #pragma unroll
       for (int i = 0; i < NR; ++i) slot[i] = a.slot[i];
@@ -257,31 +236,15 @@ __global__ __launch_bounds__(64 * kBcWaves) __attribute__((amdgpu_waves_per_eu(
     for (int i = 0; i < K; ++i) {
       dev::bs_transpose8(&x[8 * i]);
       uint32_t(&pl)[8] = *reinterpret_cast<uint32_t(*)[8]>(&x[8 * i]);
-      if constexpr (!CRC) {
-      } else if constexpr (LI) {
-        uint32_t* ri = rin + (wave * NL + i) * 64 + lane;
-        uint32_t v = fresh ? 0u : (CFSEC_BC_PROBE & 4) ? *ri : bc_five7(tb + kBcJump * 32, *ri);
-        if constexpr (!(CFSEC_BC_PROBE & 1)) v ^= bc_planes(tb, pl);
-        *ri = v;
-      } else {
-        if constexpr (!(CFSEC_BC_PROBE & 1)) R[i] ^= bc_planes(tb, pl);
-        asm volatile("" : "+v"(R[i]));
-      }
+      if constexpr (CRC)
+        bc_take<LI, false>(tb, LI ? rin + (wave * NL + i) * 64 + lane : &R[i], fresh, pl);
       __builtin_amdgcn_sched_barrier(0);
     }
     if constexpr (Net::Paired) dev::bs_pair_basis<K>(x);
     __builtin_amdgcn_sched_barrier(0);
     Net::template net<M>(x, [&](int r, uint32_t (&o)[8]) {
-      if constexpr (!CRC) {
-      } else if constexpr (LO) {
-        uint32_t* ri = rin + (wave * NL + lds_row(K + r)) * 64 + lane;
-        uint32_t v = fresh ? 0u : (CFSEC_BC_PROBE & 4) ? *ri : bc_five7(tb + kBcJump * 32, *ri);
-        if constexpr (!(CFSEC_BC_PROBE & 2)) v ^= bc_planes(tb, o);
-        *ri = v;
-      } else {
-        if constexpr (!(CFSEC_BC_PROBE & 2)) R[K + r] ^= bc_planes(tb, o);
-        asm volatile("" : "+v"(R[K + r]));
-      }
+      if constexpr (CRC)
+        bc_take<LO, true>(tb, LO ? rin + (wave * NL + lds_row(K + r)) * 64 + lane : &R[K + r], fresh, o);
       dev::bs_transpose8(o);
       uint8_t* p = out_row(s, r);
       if constexpr (FULL) {
@@ -309,7 +272,7 @@ __global__ __launch_bounds__(64 * kBcWaves) __attribute__((amdgpu_waves_per_eu(
       if constexpr (CRC) {
 #pragma unroll
         for (int i = 0; i < NR; ++i)
-          if (!in_lds(i) && !(CFSEC_BC_PROBE & 4)) R[i] = bc_five7(tb + kBcJump * 32, R[i]);
+          if (!in_lds(i)) R[i] = bc_jump(tb, R[i]);
       }
       fresh = false;
     }
@@ -335,7 +298,7 @@ __global__ __launch_bounds__(64 * kBcWaves) __attribute__((amdgpu_waves_per_eu(
           const uint32_t keep = !halving ? v[i] : (up ? v[half + i] : v[i]);
           const uint32_t recv = (uint32_t)__shfl_xor((int)send, 1 << k, 64);
           const uint32_t lo = up ? recv : keep, hi = up ? keep : recv;
-          v[i] = bc_five7(tb + (kBcTree + k * kBcFields) * 32, lo) ^ hi;
+          v[i] = five7(tb + (kBcTree + k * kBcFields) * 32, lo) ^ hi;
         }
         __builtin_amdgcn_sched_barrier(0);
       }
@@ -344,49 +307,66 @@ __global__ __launch_bounds__(64 * kBcWaves) __attribute__((amdgpu_waves_per_eu(
     // lane l holds row bitrev(l mod NP) (log2(NP) bits)
     const uint32_t row = __builtin_bitreverse32(lane & (NP - 1u)) >> (32 - LG);
     const uint32_t e = tps - 1 - c;
-    const uint32_t k = bc_mulmod(bc_mulmod(a.pw[0][e % kBcPow], a.pw[1][(e / kBcPow) % kBcPow]),
-                                 a.pw[2][e / (kBcPow * kBcPow)]);
-    uint32_t w = bc_mulmod(mine, k);
+    const uint32_t k = crcdev::mulmod(crcdev::mulmod(a.pw[0][e % kBcPow], a.pw[1][(e / kBcPow) % kBcPow]),
+                                      a.pw[2][e / (kBcPow * kBcPow)]);
+    uint32_t w = crcdev::mulmod(mine, k);
     if (!tailw && j == 0) w ^= a.fin;
     if (lane < (uint32_t)NP && row < (uint32_t)NR) atomicXor(a.crc + (size_t)s * a.crc_stride + slot[row], w);
   }
 }
 
 
+}  // namespace
+
 // ---- host side ----
-uint32_t env_mask(const char* name, uint32_t dflt) {
-  const char* v = std::getenv(name);
-  return v && *v ? (uint32_t)std::strtoul(v, nullptr, 0) : dflt;
-}
-// CFSEC_BS_CRC: bit 0 EC6P10L2's fused LRC encode (6 x 12), bit 1 EC12P4 (12 x 4; bit 3 the same),
-// bit 2 EC16P20 / EC16P20L2 (16 x 20 / 22), bit 4 EC6P8, EC6P10, EC12P9, EC15P12, EC10P4, EC4P4,
-// EC3P3 and the LRC modes EC6P3L3, EC4P4L2, EC6P6L9, EC6P8L10 (the product + separate pass, or for
-// EC6P3L3 the v_perm fused kernel, otherwise), bit 5 the product alone for EC6P6L9 / EC6P8L10's plain
-// fused encodes, bit 6 EC6P6 and EC16P4 (the EC6P10L2 / 16 + 20 networks' first rows; their v_perm
-// fused kernels before: EC6P6's 1 MiB-blob put 152 -> 131 us, EC16P4 105 -> 103, the put-batch probe
-// 124 -> 117, profiles/r06/bs_crc/ec6p6_ec16p4_ab.txt) -- all on by default --, bit 7 EC6P3 (off: 62 vs
-// 64 us); 0 keeps the lookup-product kernels / the separate pass (A/B).
-// EC12P4 was off until the remainder tiles became tail waves: the bench's fused encode + CRC 0.484 ->
-// 0.506, the ec seam 0.478 -> 0.498 (profiles/r06/bs_crc/bench_ec12p4_tail_ab.txt); 4 MiB blobs 183 ->
-// 178 us in the shape sweep (shape_sweep_ec12p4_tail.txt)
-#ifndef CFSEC_BS_CRC_DEFAULT
-#define CFSEC_BS_CRC_DEFAULT 119
-#endif
-uint32_t bs_crc_mask() {
-  static const uint32_t v = env_mask("CFSEC_BS_CRC", CFSEC_BS_CRC_DEFAULT);
-  return v;
+// The launches of a job on the kernel above (kernels.hpp): host arithmetic only.
+BsCrcPlan plan_bs_crc(const MatVecJob& job, int resident) {
+  BsCrcPlan p{};
+  p.resident = resident > 0 ? resident : 768;
+  if (job.nstripes <= 0 || job.len == 0) return p;
+  const uint64_t tps = (job.len + kBcTile - 1) / kBcTile;
+  p.pad = (int64_t)(tps * kBcTile - job.len);
+  p.pw[0] = (int64_t)kBcTile;
+  p.pw[1] = p.pw[0] * kBcPow;
+  p.pw[2] = p.pw[1] * kBcPow;
+  const int64_t ss = job_affine_stride(job);
+  const int per = ss ? job.nstripes : kBcPtr / (job.k + job.m);
+  const uint64_t nw = (uint64_t)p.resident * kBcWaves;  // one wave of workgroups
+  for (int s0 = 0; s0 < job.nstripes; s0 += per) {
+    BsCrcStep st{};
+    st.s0 = s0;
+    st.ns = std::min(per, job.nstripes - s0);
+    st.tab = ss ? 1u : (uint32_t)st.ns;
+    st.sstride = ss;
+    st.tps = (uint32_t)tps;
+    // W waves per stripe, each taking every W-th tile (neighbouring waves on neighbouring tiles of
+    // one stripe; a wave's tiles 2048 W bytes apart, one checksum fold per wave and stripe)
+    const uint64_t W = std::min<uint64_t>(tps, std::max<uint64_t>(1, nw / (uint64_t)st.ns));
+    st.W = (uint32_t)W;
+    st.groups = (uint32_t)std::min<uint64_t>((uint64_t)st.ns, nw / W);
+    st.jump = kBcTile * W;
+    st.tblk = (uint32_t)(((uint64_t)st.groups * W + kBcWaves - 1) / kBcWaves);
+    // the remainder tps mod W: in W-strided rounds a third of the waves take one tile more, and a SIMD
+    // whose 3 waves all do leaves the launch a tile late (C4: 320 tiles per row 160 us, 321 tiles 178,
+    // profiles/r06/bs_crc/c4_tail_tiles.txt); as one tile per extra wave those tiles go wherever
+    // waves retire first: C4 187 -> 176 us per put batch, EC6P6L9 158 -> 151, EC12P9 184 -> 173,
+    // EC16P20L2 (32 x 699,051) 330 -> 305; plain products unchanged.  Always taken: a cap on the
+    // remainder, a whole round more as tail waves and fixed tiles per wave all lost
+    // (profiles/r06/bs_crc/tail_waves_ab.txt, c4_tiles_per_wave_ab.txt)
+    st.tail = (uint32_t)(tps % W);
+    st.bend = st.tps - st.tail;
+    st.grid = st.tblk + (uint32_t)(((uint64_t)st.tail * st.ns + kBcWaves - 1) / kBcWaves);
+    p.steps.push_back(st);
+  }
+  return p;
 }
 
-template <class Net>
-bool rows_equal(const uint8_t* coef, int m) {
-  const uint8_t* w = Net::rows();
-  return std::memcmp(coef, w, (size_t)m * Net::K) == 0;
-}
+namespace {
 
 // f(0, one byte b)
 uint32_t crc_byte(uint32_t b) {
   uint32_t c = b;
-  for (int q = 0; q < 8; ++q) c = (c & 1u) ? (c >> 1) ^ kBcPoly : c >> 1;
+  for (int q = 0; q < 8; ++q) c = (c & 1u) ? (c >> 1) ^ crcdev::kPoly : c >> 1;
   return c;
 }
 
@@ -422,242 +402,185 @@ std::vector<uint32_t> bc_host_tables() {
   return t;
 }
 
-struct BcDev {
-  std::mutex mu;
-  uint32_t* tab = nullptr;
-};
-
-hipError_t bc_device(const uint32_t** tab) {
-  static BcDev per[64];
+hipError_t bc_device(const uint32_t** tab) {  // the table block on the current device, uploaded once
+  static std::mutex mu;
+  static std::map<int, uint32_t*> per;
   int d = 0;
   hipError_t e = hipGetDevice(&d);
   if (e != hipSuccess) return e;
-  if (d < 0 || d >= 64) return hipErrorInvalidDevice;
-  BcDev& c = per[d];
-  std::lock_guard<std::mutex> lk(c.mu);
-  const auto upload = [&](const std::vector<uint32_t>& h, uint32_t** out) -> hipError_t {
+  std::lock_guard<std::mutex> lk(mu);
+  auto it = per.find(d);
+  if (it == per.end()) {
+    const std::vector<uint32_t> h = bc_host_tables();
     uint32_t* p = nullptr;
-    hipError_t r = hipMalloc(reinterpret_cast<void**>(&p), h.size() * 4);
-    if (r != hipSuccess) return r;
-    if ((r = hipMemcpy(p, h.data(), h.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) {
+    if ((e = hipMalloc(reinterpret_cast<void**>(&p), h.size() * 4)) != hipSuccess) return e;
+    if ((e = hipMemcpy(p, h.data(), h.size() * 4, hipMemcpyHostToDevice)) != hipSuccess) {
       (void)hipFree(p);
-      return r;
+      return e;
     }
-    *out = p;
-    return hipSuccess;
-  };
-  if (!c.tab && (e = upload(bc_host_tables(), &c.tab)) != hipSuccess) return e;
-  *tab = c.tab;
+    it = per.emplace(d, p).first;
+  }
+  *tab = it->second;
   return hipSuccess;
 }
 
-int64_t bc_affine_stride(const MatVecJob& job) {  // as gf_crc.hip's
-  if (job.nstripes < 2) return 0;
-  const auto addr = [](const void* p) { return (int64_t)(uintptr_t)p; };
-  const int64_t ss = addr(job.in[job.k]) - addr(job.in[0]);
-  if (ss == 0) return 0;
-  for (int s = 1; s < job.nstripes; ++s) {
-    for (int c = 0; c < job.k; ++c)
-      if (addr(job.in[(size_t)s * job.k + c]) != addr(job.in[c]) + s * ss) return 0;
-    for (int r = 0; r < job.m; ++r)
-      if (addr(job.out[(size_t)s * job.m + r]) != addr(job.out[r]) + s * ss) return 0;
-  }
-  return ss;
-}
-
-template <class Net, int M, bool CRC = true>
-int bc_groups() {  // resident workgroups on the device (one wave of workgroups)
+// Resident workgroups of kernel f on the current device (one wave of workgroups), cached per device;
+// 0: not known (the plan then takes its fallback)
+int bc_resident(const void* f) {
   static std::mutex mu;
-  static std::map<int, int> cache;
+  static std::map<std::pair<int, const void*>, int> cache;
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return 0;
   std::lock_guard<std::mutex> l(mu);
-  auto it = cache.find(dev);
+  auto it = cache.find({dev, f});
   if (it != cache.end()) return it->second;
   int per = 0, cus = 0;
-  const void* f = reinterpret_cast<const void*>(&gf_bs_crc_kernel<Net, M, CRC>);
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, f, 64 * kBcWaves, 0) != hipSuccess ||
       hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
     (void)hipGetLastError();
     per = 0;
   }
-  const int n = per > 0 && cus > 0 ? per * cus : 768;
-  cache.emplace(dev, n);
+  const int n = per > 0 && cus > 0 ? per * cus : 0;
+  cache.emplace(std::make_pair(dev, f), n);
   return n;
 }
 
+// Plan, fill the argument block, launch -- once per step of the plan
 template <class Net, int M, bool CRC = true>
 hipError_t bc_launch(const MatVecJob& job, uint32_t* crc, int crc_stride, const int* slot, hipStream_t st) {
   constexpr int K = Net::K;
   BcArgs a{};
   hipError_t e = bc_device(&a.tabs);
   if (e != hipSuccess) return e;
-  const uint64_t len = job.len;
-  const uint64_t tps = (len + kBcTile - 1) / kBcTile;
-  const int64_t pad = (int64_t)(tps * kBcTile - len);
-  const uint32_t x1 = crc_xpow(8 * (int64_t)kBcTile), x64 = crc_xpow(8 * (int64_t)kBcTile * kBcPow),
-                 x4096 = crc_xpow(8 * (int64_t)kBcTile * kBcPow * kBcPow);
-  uint32_t p0 = crc_xpow(-8 * pad), p1 = 0x80000000u, p2 = 0x80000000u;
-  for (int i = 0; i < kBcPow; ++i) {
-    a.pw[0][i] = p0;
-    a.pw[1][i] = p1;
-    a.pw[2][i] = p2;
-    p0 = crc_mulmod(p0, x1);
-    p1 = crc_mulmod(p1, x64);
-    p2 = crc_mulmod(p2, x4096);
-  }
-  a.len = len;
-  a.tps = (uint32_t)tps;
+  const BsCrcPlan p = plan_bs_crc(job, bc_resident(reinterpret_cast<const void*>(&gf_bs_crc_kernel<Net, M, CRC>)));
+  uint32_t pw[3] = {crc_xpow(-8 * p.pad), 0x80000000u, 0x80000000u};
+  const uint32_t x[3] = {crc_xpow(8 * p.pw[0]), crc_xpow(8 * p.pw[1]), crc_xpow(8 * p.pw[2])};
+  for (int i = 0; i < kBcPow; ++i)
+    for (int d = 0; d < 3; ++d) {
+      a.pw[d][i] = pw[d];
+      pw[d] = crc_mulmod(pw[d], x[d]);
+    }
+  a.len = job.len;
   a.crc_stride = (uint32_t)crc_stride;
-  a.fin = crc32_shift_ones((size_t)len);
+  a.fin = crc32_shift_ones(job.len);
   if (CRC)
     for (int i = 0; i < K + M; ++i) a.slot[i] = (uint8_t)slot[i];
-  const int64_t ss = bc_affine_stride(job);
-  a.sstride = ss;
-  const int per = ss ? job.nstripes : kBcPtr / (K + M);
-  const int groups = bc_groups<Net, M, CRC>();
-  for (int s0 = 0; s0 < job.nstripes; s0 += per) {
-    const int ns = std::min(per, job.nstripes - s0);
-    const int tab = ss ? 1 : ns;
-    a.tab = (uint32_t)tab;
-    a.crc = CRC ? crc + (size_t)s0 * crc_stride : nullptr;
-    for (int s = 0; s < tab; ++s) {
-      for (int c = 0; c < K; ++c) a.ptr[s * K + c] = job.in[(size_t)(s0 + s) * K + c];
-      for (int r = 0; r < M; ++r) a.ptr[tab * K + s * M + r] = job.out[(size_t)(s0 + s) * M + r];
+  const bool trace = env_u32("CFSEC_TRACE_CRC", 0) != 0;
+  for (const BsCrcStep& s : p.steps) {
+    a.sstride = s.sstride;
+    a.tab = s.tab;
+    a.crc = CRC ? crc + (size_t)s.s0 * crc_stride : nullptr;
+    for (uint32_t t = 0; t < s.tab; ++t) {
+      for (int c = 0; c < K; ++c) a.ptr[t * K + c] = job.in[(size_t)(s.s0 + t) * K + c];
+      for (int r = 0; r < M; ++r) a.ptr[s.tab * K + t * M + r] = job.out[(size_t)(s.s0 + t) * M + r];
     }
-    const uint64_t nt = tps * (uint64_t)ns;
-    a.ntiles = (uint32_t)nt;
-    // W waves per stripe, each taking every W-th tile (neighbouring waves on neighbouring tiles of
-    // one stripe; a wave's tiles 2048 W bytes apart, one checksum fold per wave and stripe)
-    const uint64_t nw = (uint64_t)groups * kBcWaves;
-    uint64_t W = std::min<uint64_t>(tps, std::max<uint64_t>(1, nw / (uint64_t)ns));
-    static const uint32_t tpw_env = env_mask("CFSEC_BC_TPW", 0);  // tiles per wave and stripe (A/B)
-    if (tpw_env) W = std::min<uint64_t>(nw, (tps + tpw_env - 1) / tpw_env);
-    const uint64_t ng = std::min<uint64_t>((uint64_t)ns, nw / W);
-    a.nst = (uint32_t)ns;
-    a.wps = (uint32_t)W;
-    a.groups = (uint32_t)ng;
-    a.xjump = crc_xpow(8 * (int64_t)kBcTile * (int64_t)W);
-    unsigned grid = (unsigned)((ng * W + kBcWaves - 1) / kBcWaves);
-    // the remainder tps mod W: in W-strided rounds a third of the waves take one tile more, and a SIMD
-    // whose 3 waves all do leaves the launch a tile late (C4: 320 tiles per row 160 us, 321 tiles 178,
-    // profiles/r06/bs_crc/c4_tail_tiles.txt); as one tile per extra wave those tiles go wherever
-    // waves retire first: C4 187 -> 176 us per put batch, EC6P6L9 158 -> 151, EC12P9 184 -> 173,
-    // EC16P20L2 (32 x 699,051) 330 -> 305; moving a whole round more to tail waves: 181 (C4); plain
-    // products unchanged (profiles/r06/bs_crc/tail_waves_ab.txt).  CFSEC_BC_TAIL: the largest remainder
-    // (percent of W) taken this way (0: the strided rounds only)
-    static const uint32_t tail_pct = env_mask("CFSEC_BC_TAIL", 100);
-    const uint64_t rem = tps % W;
-    a.bend = (uint32_t)tps;
-    a.tail = 0;
-    a.tblk = grid;
-    if (rem && rem * 100 <= (uint64_t)tail_pct * W) {
-      a.bend = (uint32_t)(tps - rem);
-      a.tail = (uint32_t)rem;
-      grid += (unsigned)((rem * ns + kBcWaves - 1) / kBcWaves);
-    }
-    if (env_mask("CFSEC_TRACE_CRC", 0))
-      std::fprintf(stderr, "cfsec: bs launch stripes=%d tps=%llu W=%llu groups=%llu tail=%u\n", ns,
-                   (unsigned long long)tps, (unsigned long long)W, (unsigned long long)ng, a.tail);
-    hipLaunchKernelGGL((gf_bs_crc_kernel<Net, M, CRC>), dim3(grid), dim3(64 * kBcWaves), 0, st, a);
+    a.tps = s.tps;
+    a.ntiles = (uint32_t)((uint64_t)s.tps * s.ns);
+    a.nst = (uint32_t)s.ns;
+    a.wps = s.W;
+    a.groups = s.groups;
+    a.xjump = crc_xpow(8 * (int64_t)s.jump);
+    a.bend = s.bend;
+    a.tail = s.tail;
+    a.tblk = s.tblk;
+    if (trace)
+      std::fprintf(stderr, "cfsec: bs launch stripes=%d tps=%u W=%u groups=%u resident=%d tail=%u\n", s.ns, s.tps, s.W,
+                   s.groups, p.resident, s.tail);
+    hipLaunchKernelGGL((gf_bs_crc_kernel<Net, M, CRC>), dim3(s.grid), dim3(64 * kBcWaves), 0, st, a);
     if ((e = hipGetLastError()) != hipSuccess) return e;
   }
   return hipSuccess;
 }
 
+// The networks, one entry per (k, m) -- 6 x 6 has two, tried in turn: a job's matrix must equal the
+// first m rows of rows().  bits: the entry's CFSEC_BS_CRC bits -- bit 0 EC6P10L2's fused LRC encode,
+// bit 1 EC12P4 (bit 3 the same), bit 2 EC16P20 / EC16P20L2, bit 4 the other RS modes' encodes (EC6P8 /
+// EC6P10 on the EC6P10L2 network's first rows) and the other LRC modes' fused encodes (the product +
+// separate pass, or for EC6P3L3 the v_perm fused kernel, otherwise), bit 6 EC6P6 and EC16P4 (the
+// EC6P10L2 / 16 + 20 networks' first rows; their v_perm fused kernels before: EC6P6's 1 MiB-blob put
+// 152 -> 131 us, EC16P4 105 -> 103, profiles/r06/bs_crc/ec6p6_ec16p4_ab.txt) -- all on by default --,
+// bit 7 EC6P3 (off: 62 vs 64 us); 0 keeps the lookup-product kernels / the separate pass (A/B).
+// EC12P4 was off until the remainder tiles became tail waves: the bench's fused encode + CRC 0.484 ->
+// 0.506 (profiles/r06/bs_crc/bench_ec12p4_tail_ab.txt).  plain (bit 5): the product alone, for the
+// wide LRC modes' fused encodes, which over the fixed-K kernels' 12 outputs ran as two products: a
+// 32-bid put batch 173 -> 117 and 190 -> 128 us (profiles/r06/bs_crc/lrc_modes_put_batch.txt).
+using BcLaunch = hipError_t (*)(const MatVecJob&, uint32_t*, int, const int*, hipStream_t);
+struct BcNet {
+  int k, m;
+  uint32_t bits;
+  const uint8_t* (*rows)();
+  BcLaunch crc, plain;
+};
+template <class Net, int M, bool PLAIN = false>
+constexpr BcNet bc_net(uint32_t bits) {
+  BcLaunch plain = nullptr;
+  if constexpr (PLAIN) plain = &bc_launch<Net, M, false>;
+  return {Net::K, M, bits, &Net::rows, &bc_launch<Net, M>, plain};
+}
+constexpr uint32_t kBcDefaultMask = 119, kBcPlainBit = 32;
+constexpr BcNet kBcNets[] = {
+    bc_net<dev::BsEc6p10l2, 12>(1),     bc_net<dev::BsEc12p4, 4>(2 | 8),     bc_net<dev::BsEc16p20l2, 20>(4),
+    bc_net<dev::BsEc16p20l2, 22>(4),    bc_net<dev::BsEc6p10l2, 8>(16),      bc_net<dev::BsEc6p10l2, 10>(16),
+    bc_net<dev::BsEc12p9, 9>(16),       bc_net<dev::BsEc15p12, 12>(16),      bc_net<dev::BsEc10p4, 4>(16),
+    bc_net<dev::BsEc4p4, 4>(16),        bc_net<dev::BsEc3p3, 3>(16),         bc_net<dev::BsEc6p3l3, 6>(16),
+    bc_net<dev::BsEc4p4l2, 6>(16),      bc_net<dev::BsEc6p6l9, 15, true>(16), bc_net<dev::BsEc6p8l10, 18, true>(16),
+    bc_net<dev::BsEc6p10l2, 6>(64),     bc_net<dev::BsEc16p20l2, 4>(64),     bc_net<dev::BsEc6p10l2, 3>(128),
+};
+
+// The first entry the mask enables whose rows the job's matrix equals (plain: the product alone)
+const BcNet* bc_find(int k, int m, const uint8_t* coef, bool plain) {
+  static const uint32_t mask = env_u32("CFSEC_BS_CRC", kBcDefaultMask);
+  if (!coef) return nullptr;
+  for (const BcNet& n : kBcNets)
+    if (n.k == k && n.m == m && (plain ? n.plain && (mask & kBcPlainBit) : (mask & n.bits) != 0) &&
+        std::memcmp(coef, n.rows(), (size_t)m * k) == 0)
+      return &n;
+  return nullptr;
+}
+
+// The kernel's range: at most 64^3 tiles per row (the three power tables) and 2^32 - 1 over the stripes
+bool bs_in_range(uint64_t len, int nstripes) {
+  const uint64_t tps = (len + kBcTile - 1) / kBcTile;
+  return len != 0 && tps <= (uint64_t)kBcPow * kBcPow * kBcPow && tps * (uint64_t)std::max(nstripes, 1) <= 0xFFFFFFFFull;
+}
+
+void bc_trace(const char* what, const MatVecJob& job) {
+  if (env_u32("CFSEC_TRACE_CRC", 0))  // read per call: tests turn it on mid-process
+    std::fprintf(stderr, "cfsec: bs %s k=%d m=%d stripes=%d len=%llu\n", what, job.k, job.m, job.nstripes,
+                 (unsigned long long)job.len);
+}
+
 }  // namespace
 
-bool bs_crc_matches(int k, int m, const uint8_t* coef) {
-  if (!coef) return false;
-  const uint32_t mask = bs_crc_mask();
-  if ((mask & 1u) && k == 6 && m == 12) return rows_equal<dev::BsEc6p10l2>(coef, 12);
-  if ((mask & 10u) && k == 12 && m == 4) return rows_equal<dev::BsEc12p4>(coef, 4);
-  if ((mask & 4u) && k == 16 && (m == 20 || m == 22)) return rows_equal<dev::BsEc16p20l2>(coef, m);
-  if (mask & 16u) {  // the other RS modes' encodes (EC6P8 / EC6P10 on the EC6P10L2 network's first rows;
-                     // EC6P6, EC16P4, EC6P3: bits 6, 7 below)
-    if (k == 6 && (m == 8 || m == 10)) return rows_equal<dev::BsEc6p10l2>(coef, m);
-    if (k == 12 && m == 9) return rows_equal<dev::BsEc12p9>(coef, 9);
-    if (k == 15 && m == 12) return rows_equal<dev::BsEc15p12>(coef, 12);
-    if (k == 10 && m == 4) return rows_equal<dev::BsEc10p4>(coef, 4);
-    if (k == 4 && m == 4) return rows_equal<dev::BsEc4p4>(coef, 4);
-    if (k == 3 && m == 3) return rows_equal<dev::BsEc3p3>(coef, 3);
-    // the other LRC modes' fused encodes (global + every AZ's local rows over the data)
-    if (k == 6 && m == 6 && rows_equal<dev::BsEc6p3l3>(coef, 6)) return true;
-    if (k == 4 && m == 6) return rows_equal<dev::BsEc4p4l2>(coef, 6);
-    if (k == 6 && m == 15) return rows_equal<dev::BsEc6p6l9>(coef, 15);
-    if (k == 6 && m == 18) return rows_equal<dev::BsEc6p8l10>(coef, 18);
-  }
-  // EC6P6 and EC16P4 (bit 6), EC6P3 (bit 7): the first rows of the EC6P10L2 / 16 + 20 networks
-  if ((mask & 64u) && k == 6 && m == 6) return rows_equal<dev::BsEc6p10l2>(coef, 6);
-  if ((mask & 64u) && k == 16 && m == 4) return rows_equal<dev::BsEc16p20l2>(coef, 4);
-  if ((mask & 128u) && k == 6 && m == 3) return rows_equal<dev::BsEc6p10l2>(coef, 3);
-  return false;
+bool bs_crc_matches(int k, int m, const uint8_t* coef) { return bc_find(k, m, coef, false) != nullptr; }
+bool bs_plain_matches(int k, int m, const uint8_t* coef) { return bc_find(k, m, coef, true) != nullptr; }
+
+bool bs_crc_takes(const MatVecJob& job, int crc_stride, const int* slot) {
+  return slot && slot[0] >= 0 && crc_stride <= 256 && bs_in_range(job.len, job.nstripes) &&
+         bs_crc_matches(job.k, job.m, job.coef);
 }
 
 hipError_t launch_bs_crc(const MatVecJob& job, uint32_t* crc, int crc_stride, const int* slot, hipStream_t st) {
-  if (!crc || !slot || !bs_crc_matches(job.k, job.m, job.coef) || job.len == 0 ||
-      (job.len + kBcTile - 1) / kBcTile > (uint64_t)kBcPow * kBcPow * kBcPow ||
-      (job.len + kBcTile - 1) / kBcTile * (uint64_t)std::max(job.nstripes, 1) > 0xFFFFFFFFull || crc_stride > 256)
-    return hipErrorInvalidValue;
+  const BcNet* n = crc && slot && crc_stride <= 256 && bs_in_range(job.len, job.nstripes)
+                       ? bc_find(job.k, job.m, job.coef, false) : nullptr;
+  if (!n) return hipErrorInvalidValue;
   for (int i = 0; i < job.k + job.m; ++i)
     if (slot[i] < 0 || slot[i] >= crc_stride) return hipErrorInvalidValue;
-  if (env_mask("CFSEC_TRACE_CRC", 0))  // read per call: tests turn it on mid-process
-    std::fprintf(stderr, "cfsec: bs crc k=%d m=%d stripes=%d len=%llu\n", job.k, job.m, job.nstripes,
-                          (unsigned long long)job.len);
-  if (job.k == 6 && job.m == 12) return bc_launch<dev::BsEc6p10l2, 12>(job, crc, crc_stride, slot, st);
-  if (job.k == 6 && job.m == 6 && rows_equal<dev::BsEc6p3l3>(job.coef, 6))
-    return bc_launch<dev::BsEc6p3l3, 6>(job, crc, crc_stride, slot, st);
-  if (job.k == 6 && job.m == 6) return bc_launch<dev::BsEc6p10l2, 6>(job, crc, crc_stride, slot, st);
-  if (job.k == 6 && job.m == 3) return bc_launch<dev::BsEc6p10l2, 3>(job, crc, crc_stride, slot, st);
-  if (job.k == 16 && job.m == 4) return bc_launch<dev::BsEc16p20l2, 4>(job, crc, crc_stride, slot, st);
-  if (job.k == 6 && job.m == 15) return bc_launch<dev::BsEc6p6l9, 15>(job, crc, crc_stride, slot, st);
-  if (job.k == 6 && job.m == 18) return bc_launch<dev::BsEc6p8l10, 18>(job, crc, crc_stride, slot, st);
-  if (job.k == 4 && job.m == 6) return bc_launch<dev::BsEc4p4l2, 6>(job, crc, crc_stride, slot, st);
-  if (job.k == 6 && job.m == 10) return bc_launch<dev::BsEc6p10l2, 10>(job, crc, crc_stride, slot, st);
-  if (job.k == 6) return bc_launch<dev::BsEc6p10l2, 8>(job, crc, crc_stride, slot, st);
-  if (job.k == 12 && job.m == 9) return bc_launch<dev::BsEc12p9, 9>(job, crc, crc_stride, slot, st);
-  if (job.k == 15) return bc_launch<dev::BsEc15p12, 12>(job, crc, crc_stride, slot, st);
-  if (job.k == 10) return bc_launch<dev::BsEc10p4, 4>(job, crc, crc_stride, slot, st);
-  if (job.k == 4) return bc_launch<dev::BsEc4p4, 4>(job, crc, crc_stride, slot, st);
-  if (job.k == 3) return bc_launch<dev::BsEc3p3, 3>(job, crc, crc_stride, slot, st);
-  if (job.k == 16 && job.m == 22) return bc_launch<dev::BsEc16p20l2, 22>(job, crc, crc_stride, slot, st);
-  if (job.k == 16) return bc_launch<dev::BsEc16p20l2, 20>(job, crc, crc_stride, slot, st);
-  return bc_launch<dev::BsEc12p4, 4>(job, crc, crc_stride, slot, st);
+  bc_trace("crc", job);
+  return n->crc(job, crc, crc_stride, slot, st);
 }
 
-// The product alone on the bit-sliced kernel for the wide LRC modes' fused encodes (EC6P6L9 6 x 15,
-// EC6P8L10 6 x 18: over the fixed-K kernels' 12 outputs they ran as two products): a 32-bid put batch
-// (32 x 699,051 B) 173 -> 117 and 190 -> 128 us (profiles/r06/bs_crc/lrc_modes_put_batch.txt);
-// CFSEC_BS_CRC bit 5
-bool bs_plain_matches(int k, int m, const uint8_t* coef) {
-  if (!coef || !(bs_crc_mask() & 32u) || k != 6) return false;
-  if (m == 15) return rows_equal<dev::BsEc6p6l9>(coef, 15);
-  if (m == 18) return rows_equal<dev::BsEc6p8l10>(coef, 18);
-  return false;
-}
-
-// ... within the kernel's range: one length, at most 64^3 tiles per row and 2^32 - 1 over the stripes
-// (launch_matvec keeps the fixed-K kernels for the rest)
+// ... one length (launch_matvec keeps the fixed-K kernels for the rest)
 bool bs_plain_takes(const MatVecJob& job) {
-  if (job.len == 0 || job.lens || !bs_plain_matches(job.k, job.m, job.coef)) return false;
-  const uint64_t tps = (job.len + kBcTile - 1) / kBcTile;
-  return tps <= (uint64_t)kBcPow * kBcPow * kBcPow && tps * (uint64_t)std::max(job.nstripes, 1) <= 0xFFFFFFFFull;
+  return !job.lens && bs_in_range(job.len, job.nstripes) && bs_plain_matches(job.k, job.m, job.coef);
 }
 
 hipError_t launch_bs_plain(const MatVecJob& job, hipStream_t st) {
   // (the caller has resolved the mode to a plain store: kStore, or kStoreVerify storing every row)
-  if (!bs_plain_takes(job)) return hipErrorInvalidValue;
-  if (env_mask("CFSEC_TRACE_CRC", 0))
-    std::fprintf(stderr, "cfsec: bs plain k=%d m=%d stripes=%d len=%llu\n", job.k, job.m, job.nstripes,
-                 (unsigned long long)job.len);
-  if (job.m == 15) return bc_launch<dev::BsEc6p6l9, 15, false>(job, nullptr, 0, nullptr, st);
-  return bc_launch<dev::BsEc6p8l10, 18, false>(job, nullptr, 0, nullptr, st);
-}
-
-bool bs_crc_takes(const MatVecJob& job, int crc_stride, const int* slot) {
-  if (!slot || slot[0] < 0 || job.len == 0 || crc_stride > 256 || !bs_crc_matches(job.k, job.m, job.coef)) return false;
-  const uint64_t tps = (job.len + kBcTile - 1) / kBcTile;
-  return tps <= (uint64_t)kBcPow * kBcPow * kBcPow && tps * (uint64_t)std::max(job.nstripes, 1) <= 0xFFFFFFFFull;
+  const BcNet* n = bs_plain_takes(job) ? bc_find(job.k, job.m, job.coef, true) : nullptr;
+  if (!n) return hipErrorInvalidValue;
+  bc_trace("plain", job);
+  return n->plain(job, nullptr, 0, nullptr, st);
 }
 
 }  // namespace cfsec

@@ -48,20 +48,9 @@ uint32_t xpow(int64_t e) {
 }
 
 std::vector<uint32_t> host_tables() {
-  std::vector<uint32_t> t(crcdev::kTabWords + crcdev::kBasisWords + crcdev::kShiftWords);
+  std::vector<uint32_t> t(crcdev::kShiftBase + crcdev::kShiftWords);
   const uint32_t k4096 = xpow(8 * 4096);
-  for (int j = 0; j < 16; ++j)  // Fj[b] = f(0, 16-byte piece with byte j = b, the rest 0)
-    for (uint32_t b = 0; b < 256; ++b) {
-      uint32_t c = 0;
-      for (int i = 0; i < 16; ++i) {
-        c ^= i == j ? b : 0u;
-        for (int q = 0; q < 8; ++q) c = (c & 1u) ? (c >> 1) ^ crcdev::kPoly : c >> 1;
-      }
-      t[j * 256 + b] = c;
-    }
-  for (int q = 0; q < 4; ++q)  // Gq[b] = shift(b << 8q, 4096)
-    for (uint32_t b = 0; b < 256; ++b) t[(16 + q) * 256 + b] = mulmod(k4096, b << (8 * q));
-  uint32_t* nt = t.data() + crcdev::kByteTabWords;
+  uint32_t* nt = t.data() + crcdev::kNibTabBase;
   for (int p = 0; p < 32; ++p)  // Np[n] = f(0, 16-byte piece with nibble p = n, the rest 0)
     for (uint32_t n = 0; n < 16; ++n) {
       uint8_t piece[16] = {};
@@ -73,9 +62,7 @@ std::vector<uint32_t> host_tables() {
       }
       nt[p * 16 + n] = c;
     }
-  for (int q = 0; q < 8; ++q)  // Hq[n] = shift(n << 4q, 4096)
-    for (uint32_t n = 0; n < 16; ++n) nt[(32 + q) * 16 + n] = mulmod(k4096, n << (4 * q));
-  uint32_t* ft = nt + crcdev::kNibTabWords;
+  uint32_t* ft = t.data() + crcdev::kFiveTabBase;
   for (int w = 0; w < 5; ++w)  // Q(w, f)[e]: word w of (d0..d3, R) = e << 5f, the rest 0
     for (int f = 0; f < crcdev::kFiveFields; ++f)
       for (uint32_t e = 0; e < (f < 6 ? 32u : 4u); ++e) {
@@ -93,8 +80,8 @@ std::vector<uint32_t> host_tables() {
       }
   for (int j = 0; j < 256; ++j) {  // basis of shift(., 16*(255-j)) for thread j
     const uint32_t kj = xpow(8LL * 16 * (255 - j));
-    for (int i = 0; i < 32; ++i) t[crcdev::kTabWords + j * 32 + i] = mulmod(kj, 1u << i);
-    t[crcdev::kTabWords + crcdev::kBasisWords + j] = kj;
+    for (int i = 0; i < 32; ++i) t[crcdev::kBasisBase + j * 32 + i] = mulmod(kj, 1u << i);
+    t[crcdev::kShiftBase + j] = kj;
   }
   return t;
 }
@@ -129,15 +116,9 @@ hipError_t crc_device_tables(const uint32_t** out) {
 uint32_t crc_xpow(int64_t e) { return xpow(e); }
 uint32_t crc_mulmod(uint32_t a, uint32_t b) { return mulmod(a, b); }
 
-namespace {
-
-uint32_t env_u32(const char* name, uint32_t dflt) {
-  const char* v = std::getenv(name);
-  return v && *v ? (uint32_t)std::strtoul(v, nullptr, 10) : dflt;
-}
-
-// As gf_kernels.hip's affine_stride, for the whole job.
-int64_t affine_stride(const MatVecJob& job) {
+// Every stripe's rows at one byte distance from the stripe before (0: not so, or a single stripe):
+// the job then goes out as one pointer set and a stride, whatever its stripe count.
+int64_t job_affine_stride(const MatVecJob& job) {
   if (job.nstripes < 2) return 0;
   const auto addr = [](const void* p) { return (int64_t)(uintptr_t)p; };
   const int64_t ss = addr(job.in[job.k]) - addr(job.in[0]);
@@ -150,6 +131,8 @@ int64_t affine_stride(const MatVecJob& job) {
   }
   return ss;
 }
+
+namespace {
 
 template <bool CIN>
 int lds_per_cu(int k, int m) {
@@ -243,14 +226,54 @@ bool matvec_crc_accepts(const MatVecJob& job, int crc_stride, const int* slot) {
   return matvec_crc_route(job, crc_stride, slot) != CrcRoute::kNone;
 }
 
+// The launches of a lookup / v_perm job (kernels.hpp): host arithmetic only.
+CrcPlan plan_matvec_crc(const MatVecJob& job, CrcRoute route, int resident) {
+  CrcPlan p{};
+  if ((route != CrcRoute::kLookup && route != CrcRoute::kVperm) || job.nstripes <= 0 || job.len == 0) return p;
+  const int k = job.k, m = job.m;
+  p.tiles = (uint32_t)((job.len + crcdev::kTile - 1) / crcdev::kTile);
+  p.sstride = job_affine_stride(job);
+  p.per = std::min(p.sstride ? job.nstripes : crcdev::kPtrSlots / (k + m), 65535);
+  // matrices of dyadic blocks the v_perm kernel has a reduced-product form for: 4 outputs of 4x4
+  // blocks (EC12P4 / EC16P4 encode, coset-aligned repairs), 6 x 6 of 2x2 blocks (EC6P6 encode);
+  // 6 x 12 is EC6P10L2's fused encode + its 18 checksums (the route: that form, inputs checksummed)
+  if (route == CrcRoute::kLookup) {
+    p.dy = -1;
+  } else if (m == 12) {
+    p.dy = 2;
+  } else if ((m == 4 && k % 4 == 0) || (k == 6 && m == 6)) {
+    const DyPlan dp = dyadic_plan(job.coef, m, k);
+    p.dy = dp.E == 0 && ((dp.B == 4 && m == 4) || (dp.B == 2 && m == 6)) ? dp.B : 0;
+  }
+  // Workgroups per launch.  The v_perm kernels: ~1024, each folding ~11 tiles per row before its
+  // per-thread basis epilogue (16 rows x 32 columns); 512 / 2048 / 4096 were 3-7 % slower
+  // (profiles/r01/crc_wgs_sweep.txt).  The lookup kernel: exactly the resident count (its 48-64 KiB
+  // LDS table allows 2-3 per CU), so no second partial wave of workgroups: 768 vs 1024 for k = 12
+  // is 200 vs 220 us.  CFSEC_CRC_GROUPS overrides (probes).
+  static const uint32_t kGroupsEnv = env_u32("CFSEC_CRC_GROUPS", 0);
+  const uint32_t total = kGroupsEnv ? kGroupsEnv : p.dy == -1 && resident > 0 ? (uint32_t)resident : 1024u;
+  const uint32_t want = std::max<uint32_t>(1, total / (uint32_t)std::min(job.nstripes, p.per));
+  const uint32_t fit = std::min<uint32_t>({p.tiles, want, (uint32_t)crcdev::kMaxGroups});
+  p.tpw = (p.tiles + fit - 1) / fit;
+  p.groups = p.grid_x = (p.tiles + p.tpw - 1) / p.tpw;
+  p.grid_y = (uint32_t)std::min(job.nstripes, p.per);
+  for (uint32_t g = 0; g < p.groups; ++g)
+    p.end.push_back((int64_t)std::min<uint64_t>((uint64_t)(g + 1) * p.tpw, p.tiles) * crcdev::kTile);
+  return p;
+}
+
+// m <= 4, k <= 16: the lookup-product kernel (gf_crc_lds_kernel; CFSEC_CRC_LDS=0 keeps the v_perm
+// kernels for A/B): EC12P4 8 x 64 MiB encode + 16 checksums 225-230 -> 200 us
+// (profiles/r03/crc_lds_ab*.txt).  EC6P10L2's fused LRC encode + 18 checksums (C4) on the same lookup
+// kernel with 16-byte entries: C4's put batch 245 -> 211 us per call against the v_perm form
+// (profiles/r06/c4_crc_lds12.txt)
 hipError_t launch_matvec_crc(const MatVecJob& job, uint32_t* crc, int crc_stride, const int* slot,
                              hipStream_t stream, bool zero) {
   const CrcRoute route = crc ? matvec_crc_route(job, crc_stride, slot) : CrcRoute::kNone;
   if (route == CrcRoute::kNone) return hipErrorInvalidValue;
   const int k = job.k, m = job.m;
   const bool cin = slot[0] >= 0;
-  const char* tr = std::getenv("CFSEC_TRACE_CRC");  // read per call: tests turn it on mid-process
-  if (tr && *tr && std::strtoul(tr, nullptr, 0))
+  if (env_u32("CFSEC_TRACE_CRC", 0))  // read per call: tests turn it on mid-process
     std::fprintf(stderr, "cfsec: crc route=%s k=%d m=%d cin=%d stripes=%d len=%llu\n", crc_route_name(route), k, m,
                  (int)cin, job.nstripes, (unsigned long long)job.len);
   hipError_t e = zero ? hipMemsetAsync(crc, 0, sizeof(uint32_t) * (size_t)crc_stride * job.nstripes, stream)
@@ -261,75 +284,38 @@ hipError_t launch_matvec_crc(const MatVecJob& job, uint32_t* crc, int crc_stride
   GfCrcArgs a{};
   e = crc_device_tables(&a.tabs);
   if (e != hipSuccess) return e;
-  const uint32_t tiles = (uint32_t)((job.len + crcdev::kTile - 1) / crcdev::kTile);
-  const int64_t sstride = affine_stride(job);
-  const int per = sstride ? job.nstripes : crcdev::kPtrSlots / (k + m);
-  const int stripes_per_launch = std::min(per, 65535);
-  for (int r = 0; r < m; ++r)
-    for (int c = 0; c < k; ++c) a.coef[r * k + c] = job.coef[(size_t)r * k + c];
-  // matrices of dyadic blocks the v_perm kernel has a reduced-product form for: 4 outputs of 4x4
-  // blocks (EC12P4 / EC16P4 encode, coset-aligned repairs), 6 x 6 of 2x2 blocks (EC6P6 encode)
-  const DyPlan dp = (m == 4 && k % 4 == 0) || (k == 6 && (m == 6 || m == 12)) ? dyadic_plan(a.coef, m, k)
-                                                                             : DyPlan{0, 0};
-#ifndef CFSEC_CRC_DY2
-#define CFSEC_CRC_DY2 1  // A/B switch for the 2x2 form
-#endif
-  int dy = dp.E == 0 && ((dp.B == 4 && m == 4) || (CFSEC_CRC_DY2 && dp.B == 2 && m == 6 && k == 6)) ? dp.B : 0;
-  if (m == 12) dy = 2;  // EC6P10L2 fused encode + its 18 checksums (the route: that form, inputs checksummed)
-  // m <= 4, k <= 16: the lookup-product kernel (gf_crc_lds_kernel; CFSEC_CRC_LDS=0 keeps the v_perm
-  // kernels for A/B): EC12P4 8 x 64 MiB encode + 16 checksums 225-230 -> 200 us
-  // (profiles/r03/crc_lds_ab*.txt)
-  // EC6P10L2's fused LRC encode + 18 checksums (C4) on the same lookup kernel with 16-byte entries
-  // (round 6): C4's put batch 245 -> 211 us per call against the v_perm form (profiles/r06/c4_crc_lds12.txt)
-  if (route == CrcRoute::kLookup) dy = -1;
-  // Workgroups per launch.  The v_perm kernels: ~1024, each folding ~11 tiles per row before its
-  // per-thread basis epilogue (16 rows x 32 columns); 512 / 2048 / 4096 were 3-7 % slower
-  // (profiles/r01/crc_wgs_sweep.txt).  The lookup kernel: exactly the resident count (its 48-64 KiB
-  // LDS table allows 2-3 per CU), so no second partial wave of workgroups: 768 vs 1024 for k = 12
-  // is 200 vs 220 us.  CFSEC_CRC_GROUPS overrides (probes).
-#ifndef CFSEC_CRC_GROUPS
-#define CFSEC_CRC_GROUPS 1024
-#endif
-  static const uint32_t kGroupsEnv = env_u32("CFSEC_CRC_GROUPS", 0);
-  uint32_t total = CFSEC_CRC_GROUPS;
-  if (dy == -1) {
+  int resident = 0;  // the lookup kernel's workgroups on the device at once (0: not known)
+  if (route == CrcRoute::kLookup) {
     const int per_cu = cin ? lds_per_cu<true>(k, m) : lds_per_cu<false>(k, m);
     int dev = 0, cus = 0;
     if (per_cu > 0 && hipGetDevice(&dev) == hipSuccess &&
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
-      total = (uint32_t)(per_cu * cus * crcdev::kLdsV);
+      resident = per_cu * cus;
   }
-  if (kGroupsEnv) total = kGroupsEnv;
-  const uint32_t want = std::max<uint32_t>(1, total / (uint32_t)std::min(job.nstripes, stripes_per_launch));
-  uint32_t groups = std::min<uint32_t>({tiles, want, (uint32_t)crcdev::kMaxGroups});
-  const uint32_t tpw = (tiles + groups - 1) / groups;
-  groups = (tiles + tpw - 1) / tpw;
-
+  const CrcPlan p = plan_matvec_crc(job, route, resident);
+  for (int r = 0; r < m; ++r)
+    for (int c = 0; c < k; ++c) a.coef[r * k + c] = job.coef[(size_t)r * k + c];
   a.len = job.len;
   a.k = (uint32_t)k;
   a.m = (uint32_t)m;
-  a.tiles = tiles;
-  a.tpw = tpw;
-  a.sstride = sstride;
+  a.tiles = p.tiles;
+  a.tpw = p.tpw;
+  a.sstride = p.sstride;
   a.fin = crc32_shift_ones(job.len);
   a.crc_stride = (uint32_t)crc_stride;
   for (int i = 0; i < k + m; ++i) a.slot[i] = (uint8_t)std::max(slot[i], 0);
-  for (uint32_t g = 0; g < groups; ++g) {
-    const int64_t end = (int64_t)std::min<uint64_t>((uint64_t)(g + 1) * tpw, tiles) * crcdev::kTile;
-    a.gconst[g] = xpow(8 * ((int64_t)job.len - end));
-  }
-  for (int s0 = 0; s0 < job.nstripes; s0 += stripes_per_launch) {
-    const int ns = std::min(stripes_per_launch, job.nstripes - s0);
-    const int tab = sstride ? 1 : ns;
+  for (uint32_t g = 0; g < p.groups; ++g) a.gconst[g] = xpow(8 * ((int64_t)job.len - p.end[g]));
+  for (int s0 = 0; s0 < job.nstripes; s0 += p.per) {
+    const int ns = std::min(p.per, job.nstripes - s0);
+    const int tab = p.sstride ? 1 : ns;
     a.tab = (uint32_t)tab;
     a.crc = crc + (size_t)s0 * crc_stride;
     for (int s = 0; s < tab; ++s) {
       for (int c = 0; c < k; ++c) a.ptr[s * k + c] = job.in[(size_t)(s0 + s) * k + c];
       for (int r = 0; r < m; ++r) a.ptr[tab * k + s * m + r] = job.out[(size_t)(s0 + s) * m + r];
     }
-    // the lookup kernel runs kLdsV virtual groups per workgroup (a trailing one past the tiles idles)
-    const dim3 grid(dy == -1 ? (groups + crcdev::kLdsV - 1) / crcdev::kLdsV : groups, (unsigned)ns);
-    e = cin ? launch_crc<true>(k, m, a, grid, stream, dy) : launch_crc<false>(k, m, a, grid, stream, dy);
+    const dim3 grid(p.grid_x, (unsigned)ns);
+    e = cin ? launch_crc<true>(k, m, a, grid, stream, p.dy) : launch_crc<false>(k, m, a, grid, stream, p.dy);
     if (e != hipSuccess) return e;
   }
   return hipSuccess;

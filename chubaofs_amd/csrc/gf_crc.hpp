@@ -15,7 +15,8 @@
 // Work split.  A workgroup owns `tpw` consecutive 4 KiB tiles of one stripe; thread j holds
 // bytes [16j, 16j+16) of every row of each tile (the fixed-K GF tile of gf_device.hpp).  Per
 // checksummed row it keeps a Horner register over its pieces, R <- f(shift(R, 4080), piece):
-// 20 independent byte-table lookups per 16 bytes (crc_step below).  After
+// 35 independent conflict-free lookups in 32-word tables per 16 bytes (crc_step5 below; the
+// lookup-product kernel further down takes the piece's part from the product's own lookups).  After
 // its last tile the thread moves R from its piece end to the tile end e (x^(8*16*(255-j)), a
 // 32-column GF(2) basis read once from global memory), the 256 threads XOR-reduce, and one
 // multiply by x^(8(S - e)) moves the sum to the shard end (a host constant per workgroup;
@@ -37,13 +38,16 @@ using dev::u32x4;
 constexpr uint32_t kPoly = 0xEDB88320u;
 constexpr int kTile = 4096;            // bytes per row per tile: 256 threads x 16 B
 constexpr int kMaxK = 18, kMaxM = 12, kPtrSlots = 96, kMaxGroups = 384;  // m = 12: EC6P10L2's fused encode
-constexpr int kByteTabWords = 20 * 256;  // F0..F15: bytes of a 16-B piece;  G0..G3: register bytes
-constexpr int kNibTabWords = 40 * 16;    // N0..N31: nibbles of a 16-B piece;  H0..H7: register nibbles
-constexpr int kFiveFields = 7;           // per 32-bit word: six 5-bit fields + one 2-bit field
-constexpr int kFiveTabWords = 5 * kFiveFields * 32;  // Q(w, f): 4 piece words + the register word
-constexpr int kTabWords = kByteTabWords + kNibTabWords + kFiveTabWords;  // device table block, the basis follows
+// The device table block (gf_crc.hip host_tables), in words: the nibble tables N0..N31 of a 16-byte
+// piece, the 5-bit tables Q(w, f) of the 4 piece words and the register word, thread j's 32 columns
+// of shift(., 16*(255-j)), then [j] = x^(8*16*(255-j)), that basis' column x^0 (coalesced).
+constexpr int kNibTabWords = 32 * 16;
+constexpr int kFiveFields = 7;  // per 32-bit word: six 5-bit fields + one 2-bit field
+constexpr int kFiveTabWords = 5 * kFiveFields * 32;
+constexpr int kNibTabBase = 0, kFiveTabBase = kNibTabWords, kRegTabBase = kFiveTabBase + 4 * kFiveFields * 32;
+constexpr int kTabWords = kNibTabWords + kFiveTabWords, kBasisBase = kTabWords;
 constexpr int kBasisWords = 256 * 32;  // thread j: the 32 columns of shift(., 16*(255-j))
-constexpr int kShiftWords = 256;  // after the basis: [j] = x^(8*16*(255-j)), its column x^0 (coalesced)
+constexpr int kShiftWords = 256, kShiftBase = kBasisBase + kBasisWords;
 
 struct __attribute__((aligned(16))) GfCrcArgs {
   uint64_t len;
@@ -51,7 +55,7 @@ struct __attribute__((aligned(16))) GfCrcArgs {
   int64_t sstride;       // affine batch: byte distance between stripes (0: explicit table)
   uint32_t tab, fin;     // stripes held in ptr[]; shift(~0, len) ^ ~0
   uint32_t* crc;         // [stripe][crc_stride] checksum words, zeroed by the launcher
-  const uint32_t* tabs;  // device: kTabWords + kBasisWords + kShiftWords
+  const uint32_t* tabs;  // the device table block
   uint32_t crc_stride, pad0;
   uint8_t slot[kMaxK + kMaxM];  // checksum word of kernel row i (inputs 0..k-1, outputs k..)
   uint8_t coef[kMaxM * kMaxK];
@@ -60,73 +64,19 @@ struct __attribute__((aligned(16))) GfCrcArgs {
 };
 static_assert(sizeof(GfCrcArgs) <= 3584, "kernel argument block must stay below 4 KiB");
 
-// Two equivalent Horner steps R <- f(shift(R, 4080), d) over a thread's next 16-byte piece d,
-// which sits 4080 bytes after its previous one.  The byte-table step costs 20 LDS reads and ~30
-// VALU; its random byte indices into 256-word tables conflict (~2.6 LDS cycles per read per lane
-// group).  The nibble-table step costs 40 conflict-free reads and ~80 VALU.  Kernels whose VALU
-// is already busy with the GF product (gf_crc_kernel) take the byte step; the CRC-only kernels
-// (crc32.hip, crc32block.hip) take the nibble step (profiles/r01/crc_nibble_ab.txt: also the
-// earlier slice-by-8 byte step, whose three dependent LDS rounds per piece cost 1-8 %).
-
-// Byte tables ct (kByteTabWords): f(shift(R, 4080), d) = shift(R, 4096) ^ f(0, d) as the XOR of
-// 20 independent words, F_j[b] = f(0, the piece with byte j = b, all else 0) and
-// G_q[b] = shift(b << 8q, 4096): one LDS round per piece instead of three dependent ones.
-__device__ __forceinline__ uint32_t crc_step(const uint32_t* ct, uint32_t r, const uint32_t (&d)[4]) {
-  const uint32_t v[5] = {d[0], d[1], d[2], d[3], r};
-  uint32_t t[20];
-#pragma unroll
-  for (int w = 0; w < 5; ++w)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) t[4 * w + j] = ct[(4 * w + j) * 256 + ((v[w] >> (8 * j)) & 0xFFu)];
-  uint32_t u[7];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) u[i] = __builtin_amdgcn_bitop3_b32(t[3 * i], t[3 * i + 1], t[3 * i + 2], 0x96);
-  u[6] = t[18] ^ t[19];
-  return __builtin_amdgcn_bitop3_b32(__builtin_amdgcn_bitop3_b32(u[0], u[1], u[2], 0x96),
-                                     __builtin_amdgcn_bitop3_b32(u[3], u[4], u[5], 0x96), u[6], 0x96);
-}
-
-// Nibble tables nt (kNibTabWords): f(shift(R, 4080), d) = shift(R, 4096) ^ f(0, d), both
-// GF(2)-linear, as the XOR of 40 words: N_p[n] = f(0, the piece with nibble p = n, all else 0)
-// for the 32 nibbles of d, H_q[n] = shift(n << 4q, 4096) for the 8 nibbles of R.  A 16-word
-// table lies in 16 distinct banks of ds_read_b32's 32, so lanes either hit distinct banks or
-// broadcast one word: no conflicts.  The 40 reads are independent (R is not folded into the
-// data first), so the Horner chain through R is one LDS round per piece.
 __device__ __forceinline__ uint32_t nib_word(const uint32_t* t, uint32_t scaled) {
   return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(t) + scaled);
 }
 
-__device__ __forceinline__ uint32_t crc_step_nib(const uint32_t* nt, uint32_t r, const uint32_t (&d)[4]) {
-  const uint32_t v[5] = {d[0], d[1], d[2], d[3], r};
-  uint32_t t[40];
-#pragma unroll
-  for (int w = 0; w < 5; ++w) {
-    // byte j of lo / hi = 4 x (low / high nibble of byte j): one byte extract per address.  The
-    // empty asm keeps the compiler from re-forming each address as its own shift + mask.
-    uint32_t lo = (v[w] << 2) & 0x3C3C3C3Cu, hi = (v[w] >> 2) & 0x3C3C3C3Cu;
-    asm volatile("" : "+v"(lo), "+v"(hi));
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      t[8 * w + 2 * j] = nib_word(nt + (8 * w + 2 * j) * 16, (lo >> (8 * j)) & 0xFFu);
-      t[8 * w + 2 * j + 1] = nib_word(nt + (8 * w + 2 * j + 1) * 16, (hi >> (8 * j)) & 0xFFu);
-    }
-  }
-  // three-input XORs (v_bitop3_b32): 40 -> 1 in 20 instructions
-  uint32_t u[14];
-#pragma unroll
-  for (int i = 0; i < 13; ++i) u[i] = __builtin_amdgcn_bitop3_b32(t[3 * i], t[3 * i + 1], t[3 * i + 2], 0x96);
-  u[13] = t[39];
-  const uint32_t a0 = __builtin_amdgcn_bitop3_b32(u[0], u[1], u[2], 0x96);
-  const uint32_t a1 = __builtin_amdgcn_bitop3_b32(u[3], u[4], u[5], 0x96);
-  const uint32_t a2 = __builtin_amdgcn_bitop3_b32(u[6], u[7], u[8], 0x96);
-  const uint32_t a3 = __builtin_amdgcn_bitop3_b32(u[9], u[10], u[11], 0x96);
-  const uint32_t a4 = __builtin_amdgcn_bitop3_b32(u[12], u[13], a0, 0x96);
-  return __builtin_amdgcn_bitop3_b32(__builtin_amdgcn_bitop3_b32(a1, a2, a3, 0x96), a4, 0u, 0x96);
-}
-
-// 5-bit tables ft (kFiveTabWords, at kByteTabWords + kNibTabWords in the device block): the same
-// step as the XOR of 35 words.  Each 32-bit word v of (d0..d3, R) is cut into fields at bits 0, 5,
-// ..., 25 (5 bits) and 30 (2 bits); Q(w, f)[e] = the step's image of word w = e << 5f, all else 0.
+// The Horner step R <- f(shift(R, 4080), d) over a thread's next 16-byte piece d, which sits 4080
+// bytes after its previous one: f(shift(R, 4080), d) = shift(R, 4096) ^ f(0, d), GF(2)-linear in
+// (d, R), taken as the XOR of independent table words -- one LDS round per piece.  The byte-table
+// (20 reads of 256-word tables, ~2.6 conflict cycles each) and nibble-table (40 conflict-free reads)
+// steps this replaced: profiles/r01/crc_nibble_ab.txt, profiles/r02/crc_only_step_ab.txt.
+//
+// 5-bit tables ft (kFiveTabWords, at kFiveTabBase in the device block): the step as the XOR of 35
+// words.  Each 32-bit word v of (d0..d3, R) is cut into fields at bits 0, 5, ..., 25 (5 bits) and
+// 30 (2 bits); Q(w, f)[e] = the step's image of word w = e << 5f, all else 0.
 // A table of at most 32 words sits in 32 distinct banks, so ds_read_b32 (2 x 32-lane groups,
 // bank = word mod 32) never conflicts: 35 LDS cycles-per-group per piece against ~20 x 3.1 for the
 // byte step (SQ_LDS_BANK_CONFLICT, profiles/r01/pmc_lds_conflicts_crc.txt) and 40 for the nibble
@@ -144,6 +94,15 @@ __device__ __forceinline__ void five_word(const uint32_t* ft, uint32_t v, uint32
                                      __builtin_amdgcn_ubfe(e, 28, 4)};
 #pragma unroll
   for (int f = 0; f < kFiveFields; ++f) t[f] = nib_word(ft + (W * kFiveFields + f) * 32, off[f]);
+}
+
+// A linear map of one word from its 7 tables at tb: the XOR of the 7 lookups (shift(r, 4096) from
+// Q(4, .); the bit-sliced kernel's plane, jump and lane-tree tables, gf_bs_crc.hip)
+__device__ __forceinline__ uint32_t five7(const uint32_t* tb, uint32_t v) {
+  uint32_t t[kFiveFields];
+  five_word<0>(tb, v, t);
+  return __builtin_amdgcn_bitop3_b32(__builtin_amdgcn_bitop3_b32(t[0], t[1], t[2], 0x96),
+                                     __builtin_amdgcn_bitop3_b32(t[3], t[4], t[5], 0x96), t[6], 0x96);
 }
 
 __device__ __forceinline__ uint32_t crc_step5(const uint32_t* ft, uint32_t r, const uint32_t (&d)[4]) {
@@ -165,40 +124,6 @@ __device__ __forceinline__ uint32_t crc_step5(const uint32_t* ft, uint32_t r, co
   return __builtin_amdgcn_bitop3_b32(a0, a1, a2 ^ a3, 0x96);
 }
 
-// The fused product+CRC kernel's step: 5-bit tables by default (CFSEC_FUSED_STEP=0: byte tables,
-// for A/B probes).
-#ifndef CFSEC_FUSED_STEP
-#define CFSEC_FUSED_STEP 1
-#endif
-#if CFSEC_FUSED_STEP
-constexpr int kFusedTabBase = kByteTabWords + kNibTabWords, kFusedTabWords = kFiveTabWords;
-__device__ __forceinline__ uint32_t fused_step(const uint32_t* ct, uint32_t r, const uint32_t (&d)[4]) {
-  return crc_step5(ct, r, d);
-}
-#else
-constexpr int kFusedTabBase = 0, kFusedTabWords = kByteTabWords;
-__device__ __forceinline__ uint32_t fused_step(const uint32_t* ct, uint32_t r, const uint32_t (&d)[4]) {
-  return crc_step(ct, r, d);
-}
-#endif
-
-// The CRC-only kernels' step (crc32.hip, crc32block.hip): 5-bit tables by default
-// (CFSEC_CRC_ONLY_STEP=0: nibble tables, for A/B probes).
-#ifndef CFSEC_CRC_ONLY_STEP
-#define CFSEC_CRC_ONLY_STEP 1
-#endif
-#if CFSEC_CRC_ONLY_STEP
-constexpr int kOnlyTabBase = kByteTabWords + kNibTabWords, kOnlyTabWords = kFiveTabWords;
-__device__ __forceinline__ uint32_t only_step(const uint32_t* ct, uint32_t r, const uint32_t (&d)[4]) {
-  return crc_step5(ct, r, d);
-}
-#else
-constexpr int kOnlyTabBase = kByteTabWords, kOnlyTabWords = kNibTabWords;
-__device__ __forceinline__ uint32_t only_step(const uint32_t* ct, uint32_t r, const uint32_t (&d)[4]) {
-  return crc_step_nib(ct, r, d);
-}
-#endif
-
 // a * b mod P (reflected: bit 31 = x^0)
 __device__ __forceinline__ uint32_t mulmod(uint32_t a, uint32_t b) {
   uint32_t p = 0;
@@ -215,16 +140,13 @@ __device__ __forceinline__ uint32_t mulmod(uint32_t a, uint32_t b) {
 // next tile when that one is full too (`next`; then `pre` says those rows are already in x).  The
 // thread holding the shard end (or past it) reads/writes only bytes < len and checksums the piece
 // zero-padded, which is what the negative group shift undoes.
-#ifndef CFSEC_CRC_LOOKAHEAD
-#define CFSEC_CRC_LOOKAHEAD 2
-#endif
 template <int K, int M, bool CIN>
 __device__ __forceinline__ void crc_tile(uint64_t len, const u32x4* tab01, const uint32_t* tab2,
                                          const uint32_t* ct, const uint8_t* const (&row)[K + M],
                                          uint32_t off, bool pre, bool next, uint32_t (&x)[K][4],
                                          uint32_t (&R)[(CIN ? K : 0) + M]) {
   constexpr int RO = CIN ? K : 0;  // register of output row 0
-  constexpr int D = CFSEC_CRC_LOOKAHEAD < K ? CFSEC_CRC_LOOKAHEAD : K;
+  constexpr int D = 2 < K ? 2 : K;  // input rows loaded ahead of the product
   static_assert(K % 2 == 0 && D % 2 == 0, "row pairs");
   uint32_t acc[M][4];
 #pragma unroll
@@ -259,8 +181,8 @@ __device__ __forceinline__ void crc_tile(uint64_t len, const u32x4* tab01, const
                          tab2 + (c + 1) * M);
       pin();
       if constexpr (CIN) {
-        R[c] = fused_step(ct, R[c], x[c]);
-        R[c + 1] = fused_step(ct, R[c + 1], x[c + 1]);
+        R[c] = crc_step5(ct, R[c], x[c]);
+        R[c + 1] = crc_step5(ct, R[c + 1], x[c + 1]);
         asm volatile("" : "+v"(R[c]), "+v"(R[c + 1]));
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -280,7 +202,7 @@ __device__ __forceinline__ void crc_tile(uint64_t len, const u32x4* tab01, const
         xv[3] = v.w;
       }
       dev::mac_row_k<M>(acc, xv, tab01 + c * M, tab2 + c * M);
-      if constexpr (CIN) R[c] = fused_step(ct, R[c], xv);
+      if constexpr (CIN) R[c] = crc_step5(ct, R[c], xv);
     }
     if (rem)
 #pragma unroll
@@ -289,7 +211,7 @@ __device__ __forceinline__ void crc_tile(uint64_t len, const u32x4* tab01, const
                      rem);
   }
 #pragma unroll
-  for (int r = 0; r < M; ++r) R[RO + r] = fused_step(ct, R[RO + r], acc[r]);
+  for (int r = 0; r < M; ++r) R[RO + r] = crc_step5(ct, R[RO + r], acc[r]);
 }
 
 // The product of a dyadic matrix in the fused kernel (gf_dyadic.hpp): 4x4 blocks for 4 outputs
@@ -351,7 +273,7 @@ __device__ __forceinline__ void crc_tile_dy(uint64_t len, const u32x4* tab01, co
       if constexpr (CIN) {
 #pragma unroll
         for (int c = B * cb; c < B * cb + B; ++c) {
-          R[c] = fused_step(ct, R[c], x[c]);
+          R[c] = crc_step5(ct, R[c], x[c]);
           asm volatile("" : "+v"(R[c]));
         }
       }
@@ -373,7 +295,7 @@ __device__ __forceinline__ void crc_tile_dy(uint64_t len, const u32x4* tab01, co
       }
       product(cb, x);
       if constexpr (CIN)
-        for (int c = 0; c < B; ++c) R[B * cb + c] = fused_step(ct, R[B * cb + c], x[c]);
+        for (int c = 0; c < B; ++c) R[B * cb + c] = crc_step5(ct, R[B * cb + c], x[c]);
     }
     if (rem)
 #pragma unroll
@@ -381,7 +303,7 @@ __device__ __forceinline__ void crc_tile_dy(uint64_t len, const u32x4* tab01, co
         dev::st_tail(const_cast<uint8_t*>(row[K + r]) + off, u32x4{acc[r][0], acc[r][1], acc[r][2], acc[r][3]}, rem);
   }
 #pragma unroll
-  for (int r = 0; r < M; ++r) R[RO + r] = fused_step(ct, R[RO + r], acc[r]);
+  for (int r = 0; r < M; ++r) R[RO + r] = crc_step5(ct, R[RO + r], acc[r]);
 }
 
 // The end of a fused kernel: every Horner register R[i] (row i of the checksummed rows, inputs first
@@ -391,7 +313,7 @@ __device__ __forceinline__ void crc_tile_dy(uint64_t len, const u32x4* tab01, co
 template <int K, int NR, bool CIN>
 __device__ __forceinline__ void crc_epilogue(const GfCrcArgs& a, const uint32_t (&R)[NR], uint32_t (&red)[4][NR],
                                              uint32_t g, uint32_t stripe, uint32_t tid, bool live = true) {
-  const u32x4* basis = reinterpret_cast<const u32x4*>(a.tabs + kTabWords + tid * 32);
+  const u32x4* basis = reinterpret_cast<const u32x4*>(a.tabs + kBasisBase + tid * 32);
   uint32_t col[32];
 #pragma unroll
   for (int q = 0; q < 8; ++q) {
@@ -429,14 +351,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DY ? 3 : 4,
   constexpr int NR = (CIN ? K : 0) + M;  // checksummed rows
   __shared__ u32x4 tab01[K * M];
   __shared__ uint32_t tab2[K * M];
-  __shared__ uint32_t ct[kFusedTabWords];
+  __shared__ uint32_t ct[kFiveTabWords];
   __shared__ uint32_t red[4][NR];
   constexpr bool kDy = DY != 0;
   if constexpr (kDy)
     dev::build_dy_tables<K, M - E, (DY ? DY : 1), (M - E) / (DY ? DY : 1), E>(a.coef, tab01, tab2);
   else
     dev::build_tables<M>(K, M, a.coef, tab01, tab2);
-  for (int i = threadIdx.x; i < kFusedTabWords; i += 256) ct[i] = a.tabs[kFusedTabBase + i];
+  for (int i = threadIdx.x; i < kFiveTabWords; i += 256) ct[i] = a.tabs[kFiveTabBase + i];
   __syncthreads();
 
   const uint32_t g = blockIdx.x, stripe = blockIdx.y;
@@ -538,14 +460,6 @@ __device__ __forceinline__ void ent_offsets(uint32_t v, uint32_t& lo, uint32_t& 
   asm volatile("" : "+v"(lo), "+v"(hi));
 }
 
-// shift(r, 4096) from the 5-bit tables of the register word (rt = Q(4, .), 7 x 32 words)
-__device__ __forceinline__ uint32_t rshift4096(const uint32_t* rt, uint32_t r) {
-  uint32_t t[kFiveFields];
-  five_word<0>(rt, r, t);
-  return __builtin_amdgcn_bitop3_b32(__builtin_amdgcn_bitop3_b32(t[0], t[1], t[2], 0x96),
-                                     __builtin_amdgcn_bitop3_b32(t[3], t[4], t[5], 0x96), t[6], 0x96);
-}
-
 // Output dwords from the byte-transposed accumulators: o[r][w] byte i = byte r of g[4w + i].
 template <int M>
 __device__ __forceinline__ void untranspose(const uint32_t (&g)[16], uint32_t (&o)[M][4]) {
@@ -565,38 +479,21 @@ __device__ __forceinline__ void untranspose(const uint32_t (&g)[16], uint32_t (&
   }
 }
 
-#ifndef CFSEC_LDS_LOOKAHEAD
-#define CFSEC_LDS_LOOKAHEAD 4
-#endif
 // Lookups in flight: the 8 reads of word step s + P are issued before word step s is consumed
 // (a step = one dword of one row's piece), so a wave keeps ~8P reads outstanding instead of
 // draining its LDS queue after every few (lgkmcnt counts to 15).  P = 0: each step's 8 reads, then
-// their use.  The 16-byte entries take P = 0 by default: P = 1 holds 64 VGPRs of entries.
-#ifndef CFSEC_LDS_PIPE
-#define CFSEC_LDS_PIPE 1
-#endif
-#ifndef CFSEC_LDS_PIPE_W
-#define CFSEC_LDS_PIPE_W 0
-#endif
-// Output rows' checksums from the 5-bit tables (35 conflict-free reads per 16-byte piece, the
-// register jump included) instead of E_0's nibble words + the jump (32 + 7).  Bit 0: the 8-byte-entry
-// kernels (m <= 4), bit 1: the 16-byte-entry kernels.
-#ifndef CFSEC_LDS_OUT5
-#define CFSEC_LDS_OUT5 0
-#endif
-template <int M>
-constexpr bool lds_out5() {
-  return (CFSEC_LDS_OUT5 >> (lds_ew(M) == 2 ? 0 : 1)) & 1;
-}
-
+// their use.  The 8-byte entries take P = 1 (-3 %), the 16-byte entries P = 0: P = 1 would hold 64
+// VGPRs of entries.  Input rows are loaded 4 rows ahead.  (Measured and gone from the source: the
+// output rows' checksums from the 5-bit tables of all five words instead of E_0's nibble words + the
+// jump, 211 -> 225-252 us on C4's put batch; two 256-thread groups sharing one E: DESIGN.md §4.2.)
 template <int K, int M, bool CIN>
-__device__ __forceinline__ void crc_tile_lds(uint64_t len, const char* E, const uint32_t* ft, const uint32_t* rt,
+__device__ __forceinline__ void crc_tile_lds(uint64_t len, const char* E, const uint32_t* rt,
                                              const uint8_t* const (&row)[K + M], uint32_t off, bool pre, bool next,
                                              uint32_t (&x)[K][4], uint32_t (&R)[(CIN ? K : 0) + M]) {
   constexpr int RO = CIN ? K : 0;
-  constexpr int D = CFSEC_LDS_LOOKAHEAD < K ? CFSEC_LDS_LOOKAHEAD : K;
+  constexpr int D = 4 < K ? 4 : K;
   constexpr int NQ = lds_nq(M), EW = lds_ew(M), EB = 4 * EW, RB = lds_row_bytes(M);
-  constexpr int P = EW == 2 ? CFSEC_LDS_PIPE : CFSEC_LDS_PIPE_W;
+  constexpr int P = EW == 2 ? 1 : 0;
   uint32_t g[16][NQ];
 #pragma unroll
   for (int p = 0; p < 16; ++p)
@@ -701,17 +598,6 @@ __device__ __forceinline__ void crc_tile_lds(uint64_t len, const char* E, const 
         if (r < mq)
           dev::st_tail(const_cast<uint8_t*>(row[K + 4 * q + r]) + off, u32x4{o[r][0], o[r][1], o[r][2], o[r][3]}, rem);
     }
-    if constexpr (lds_out5<M>()) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        if (r < mq) {
-          R[RO + 4 * q + r] = crc_step5(ft, R[RO + 4 * q + r], o[r]);
-          asm volatile("" : "+v"(R[RO + 4 * q + r]));
-        }
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      continue;
-    }
     uint32_t L[P + 1][8];
     uint32_t rs[4][kFiveFields];
 #pragma unroll
@@ -761,34 +647,16 @@ __device__ __forceinline__ void crc_tile_lds(uint64_t len, const char* E, const 
   }
 }
 
-// V: 256-thread virtual groups per workgroup, each an independent run of tiles with its own
-// epilogue; they share one copy of E (the LDS, not the registers, bounds the waves per CU).
-#ifndef CFSEC_LDS_V
-#define CFSEC_LDS_V 1
-#endif
-#ifndef CFSEC_LDS_WPE
-#define CFSEC_LDS_WPE 3
-#endif
-constexpr int kLdsV = CFSEC_LDS_V;
 template <int K, int M, bool CIN>
-__global__ __launch_bounds__(256 * kLdsV) __attribute__((amdgpu_waves_per_eu(CFSEC_LDS_WPE, 8))) void gf_crc_lds_kernel(
-    const GfCrcArgs a) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) void gf_crc_lds_kernel(const GfCrcArgs a) {
   static_assert(M >= 1 && M <= 12, "an entry holds at most 12 products");
   constexpr int NR = (CIN ? K : 0) + M;
-  constexpr int NT = 256 * kLdsV;
+  constexpr int NT = 256;
   constexpr int NQ = lds_nq(M), EW = lds_ew(M);
   __shared__ u32x4 E[K * lds_row_bytes(M) / 16];
-  constexpr bool kO5 = lds_out5<M>();
-  constexpr int kFtWords = (kO5 ? 5 : 1) * kFiveFields * 32, kGfWords = K * 32 * NQ;
-  // the register word's 5-bit tables Q(4, .) (kO5: all five words' tables, Q(4, .) last; the product
-  // words gfw, needed only while E is built, then live in the same words, so E_c + tables stay
-  // within a third of the LDS)
-  constexpr bool kShare = kO5 && kGfWords <= kFtWords;
-  __shared__ uint32_t ft[kFtWords];
-  __shared__ uint32_t gfw_own[kShare ? 1 : kGfWords];
-  uint32_t* gfw = kShare ? ft : gfw_own;
-  const uint32_t* rt = ft + (kO5 ? 4 * kFiveFields * 32 : 0);
-  __shared__ uint32_t red[kLdsV][4][NR];
+  __shared__ uint32_t rt[kFiveFields * 32];  // the register word's 5-bit tables Q(4, .)
+  __shared__ uint32_t gfw[K * 32 * NQ];      // needed only while E is built
+  __shared__ uint32_t red[4][NR];
   // gfw[(c * 32 + h * 16 + n) * NQ + q]: the products of input row c's coefficients of outputs
   // 4q .. 4q + 3 with n << 4h
   for (int i = threadIdx.x; i < K * 32 * NQ; i += NT) {
@@ -800,13 +668,11 @@ __global__ __launch_bounds__(256 * kLdsV) __attribute__((amdgpu_waves_per_eu(CFS
       if (4 * q + b < M) w |= gf_mul_dev(a.coef[(4 * q + b) * K + c], v) << (8 * b);
     gfw[i] = w;
   }
-  if constexpr (!kShare)
-    for (int i = threadIdx.x; i < kFtWords; i += NT)
-      ft[i] = a.tabs[kByteTabWords + kNibTabWords + (kO5 ? 0 : 4 * kFiveFields * 32) + i];
+  for (int i = threadIdx.x; i < kFiveFields * 32; i += NT) rt[i] = a.tabs[kRegTabBase + i];
   __syncthreads();
   // E_c[q][n] (q = 2p + h) = (N_q[n], gfw[c][h][n][..]); N_q are the device block's nibble tables
   // (entry i & 511 of E_c takes N word i & 511: a thread meets at most two of them)
-  const uint32_t* nt = a.tabs + kByteTabWords;
+  const uint32_t* nt = a.tabs + kNibTabBase;
   const uint32_t nA = nt[threadIdx.x & 511], nB = nt[(threadIdx.x + 256) & 511];
   uint32_t* Ew = reinterpret_cast<uint32_t*>(E);
   for (int i = threadIdx.x; i < K * 512; i += NT) {
@@ -818,13 +684,8 @@ __global__ __launch_bounds__(256 * kLdsV) __attribute__((amdgpu_waves_per_eu(CFS
     for (int w = 1; w < EW; ++w) dst[w] = w - 1 < NQ ? pw[w - 1] : 0u;
   }
   __syncthreads();
-  if constexpr (kShare) {
-    for (int i = threadIdx.x; i < kFtWords; i += NT) ft[i] = a.tabs[kByteTabWords + kNibTabWords + i];
-    __syncthreads();
-  }
 
-  const uint32_t vg = threadIdx.x >> 8, tid = threadIdx.x & 255;
-  const uint32_t g = blockIdx.x * kLdsV + vg, stripe = blockIdx.y;
+  const uint32_t tid = threadIdx.x, g = blockIdx.x, stripe = blockIdx.y;
   const size_t ts = a.sstride ? 0 : (size_t)stripe;
   const int64_t sbase = (int64_t)stripe * a.sstride;
   const uint8_t* row[K + M];
@@ -843,10 +704,10 @@ __global__ __launch_bounds__(256 * kLdsV) __attribute__((amdgpu_waves_per_eu(CFS
   for (uint32_t t = t0; t < t1; ++t) {
     const uint32_t off = t * kTile + lanepos;
     const bool next = t + 1 < t1 && (uint64_t)off + kTile + dev::kLaneBytes <= a.len;
-    crc_tile_lds<K, M, CIN>(a.len, reinterpret_cast<const char*>(E), ft, rt, row, off, pre, next, x, R);
+    crc_tile_lds<K, M, CIN>(a.len, reinterpret_cast<const char*>(E), rt, row, off, pre, next, x, R);
     pre = next && (uint64_t)off + dev::kLaneBytes <= a.len;
   }
-  crc_epilogue<K, NR, CIN>(a, R, red[vg], g, stripe, tid, t0 < a.tiles);
+  crc_epilogue<K, NR, CIN>(a, R, red, g, stripe, tid, t0 < a.tiles);
 }
 
 // Launch gf_crc_kernel<K, m, CIN> (instantiated for m = 1..6 in gf_crc_k<K>.hip); dy: the dyadic
@@ -859,13 +720,13 @@ hipError_t launch_crc_k(int m, const GfCrcArgs& a, dim3 grid, hipStream_t st, in
       return hipErrorInvalidValue;  // E would pass 64 KiB
     } else {
       switch (m) {
-        case 1: hipLaunchKernelGGL((gf_crc_lds_kernel<K, 1, CIN>), grid, dim3(256 * kLdsV), 0, st, a); break;
-        case 2: hipLaunchKernelGGL((gf_crc_lds_kernel<K, 2, CIN>), grid, dim3(256 * kLdsV), 0, st, a); break;
-        case 3: hipLaunchKernelGGL((gf_crc_lds_kernel<K, 3, CIN>), grid, dim3(256 * kLdsV), 0, st, a); break;
-        case 4: hipLaunchKernelGGL((gf_crc_lds_kernel<K, 4, CIN>), grid, dim3(256 * kLdsV), 0, st, a); break;
+        case 1: hipLaunchKernelGGL((gf_crc_lds_kernel<K, 1, CIN>), grid, dim3(256), 0, st, a); break;
+        case 2: hipLaunchKernelGGL((gf_crc_lds_kernel<K, 2, CIN>), grid, dim3(256), 0, st, a); break;
+        case 3: hipLaunchKernelGGL((gf_crc_lds_kernel<K, 3, CIN>), grid, dim3(256), 0, st, a); break;
+        case 4: hipLaunchKernelGGL((gf_crc_lds_kernel<K, 4, CIN>), grid, dim3(256), 0, st, a); break;
         case 12:
           if constexpr (K == 6 && CIN) {  // EC6P10L2's fused LRC encode + its 18 checksums
-            hipLaunchKernelGGL((gf_crc_lds_kernel<K, 12, CIN>), grid, dim3(256 * kLdsV), 0, st, a);
+            hipLaunchKernelGGL((gf_crc_lds_kernel<K, 12, CIN>), grid, dim3(256), 0, st, a);
             break;
           }
           return hipErrorInvalidValue;
@@ -937,7 +798,7 @@ int lds_blocks_per_cu(int m) {
       default: return 0;
     }
     int n = 0;
-    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, 256 * kLdsV, 0) == hipSuccess ? n : 0;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, 256, 0) == hipSuccess ? n : 0;
   }
 }
 

@@ -3,6 +3,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <cstdlib>
+
 #include "gf_device.hpp"
 #include "kernels.hpp"
 
@@ -127,16 +129,28 @@ hipError_t launch_bs16_repair_tab(int nd, int ne, const uint8_t* missing, const 
                                   const dev::GfArgs& a, const uint8_t* const* rows, unsigned ns, uint64_t len,
                                   hipStream_t st, bool* ok);
 
-// Fused encode + crc32.ChecksumIEEE of every row on the bit-sliced networks (gf_bs_crc.hip, round 6):
-// EC6P10L2's fused LRC encode (6 x 12) and EC12P4's encode (12 x 4), coef equal to the network's
-// constants, the inputs checksummed too (slot[0] >= 0), any row alignment and length; words as
-// launch_matvec_crc (zeroed by the caller).  CFSEC_BS_CRC (bit 0: 6 x 12, bit 1: 12 x 4) = 0 keeps
-// the lookup-product kernels.
+// An unsigned environment setting (any base strtoul reads), `dflt` when unset or empty: the A/B masks
+// and probe overrides of the fused checksum kernels.
+inline uint32_t env_u32(const char* name, uint32_t dflt) {
+  const char* v = std::getenv(name);
+  return v && *v ? (uint32_t)std::strtoul(v, nullptr, 0) : dflt;
+}
+// The byte distance between consecutive stripes when every row of the job keeps it (gf_crc.hip), else 0.
+int64_t job_affine_stride(const MatVecJob& job);
+
+// Fused encode + crc32.ChecksumIEEE of every row on the bit-sliced networks (gf_bs_crc.hip): a kStore
+// job whose coef equals the rows of one of the networks in that file's table (kBcNets: every code
+// mode's encode or fused LRC encode, each under its CFSEC_BS_CRC bits -- default 119, 0 keeps the
+// lookup-product kernels / the separate pass), the inputs checksummed too (slot[0] >= 0), any row
+// alignment, 1 <= len <= 64^3 tiles of 2 KiB and at most 2^32 - 1 tiles over the stripes
+// (bs_in_range); words as launch_matvec_crc (zeroed by the caller).  plan_bs_crc (kernels.hpp) gives
+// the launches.
 bool bs_crc_matches(int k, int m, const uint8_t* coef);
 bool bs_crc_takes(const MatVecJob& job, int crc_stride, const int* slot);
 hipError_t launch_bs_crc(const MatVecJob& job, uint32_t* crc, int crc_stride, const int* slot, hipStream_t st);
 // The product alone on the same kernel (no checksums) for the wide LRC modes' fused encodes (EC6P6L9,
-// EC6P8L10): a kStore job whose coef equals their networks, any alignment and length
+// EC6P8L10, the table entries with a plain form; CFSEC_BS_CRC bit 5): a kStore job whose coef equals
+// their networks, any alignment
 bool bs_plain_matches(int k, int m, const uint8_t* coef);
 bool bs_plain_takes(const MatVecJob& job);  // ... and one length, the tile counts within the kernel's range
 hipError_t launch_bs_plain(const MatVecJob& job, hipStream_t st);

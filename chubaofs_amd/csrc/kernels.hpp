@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 #include <cstddef>
 #include <cstdint>
+#include <vector>
 
 namespace cfsec {
 
@@ -169,6 +170,48 @@ const char* crc_route_name(CrcRoute r);  // "none", "bit-sliced", "lookup", "v_p
 bool matvec_crc_accepts(const MatVecJob& job, int crc_stride, const int* slot);
 hipError_t launch_matvec_crc(const MatVecJob& job, uint32_t* crc, int crc_stride, const int* slot,
                              hipStream_t stream, bool zero = true);
+
+// The launches of the fused kernels, decided the way plan_matvec decides launch_matvec's: pure host
+// functions (no HIP calls) of the job and of one device-dependent number, `resident` -- the workgroups
+// of the chosen kernel the device holds at once, which the dispatchers get from an occupancy query
+// (cached per device) and pass in.  resident <= 0 says the query failed: 768 for the bit-sliced
+// kernels, 1024 for the lookup kernel (the v_perm kernels always take 1024).
+//
+// Bit-sliced (the fused kernel and the plain product of gf_bs_crc.hip): a row is tps tiles of 2 KiB.
+// A launch takes stripes [s0, s0 + ns) -- all of an affine job (tab = 1), 96 / (k + m) of a
+// pointer-table job (tab = ns) -- with W waves per stripe in `groups` wave groups: wave j of a group
+// takes tiles j, j + W, ... below bend = W floor(tps / W) of the group's stripes, its registers
+// jumping `jump` = 2048 W bytes between them, and the stripes' last tail = tps - bend tiles go one per
+// wave to the workgroups from tblk on (4 waves per workgroup).  CFSEC_TRACE_CRC prints per launch
+// "cfsec: bs launch stripes=<ns> tps=.. W=.. groups=.. resident=.. tail=..".
+struct BsCrcStep {
+  int s0, ns;
+  uint32_t tab;
+  int64_t sstride;
+  uint32_t tps, W, groups, bend, tail, tblk, grid;
+  uint64_t jump;
+};
+struct BsCrcPlan {
+  int resident;       // as used (the fallback when none was given)
+  int64_t pad;        // zero bytes after the row in its last tile
+  int64_t pw[3];      // tile e's end to the row's end is x^(8 (e0 pw[0] + e1 pw[1] + e2 pw[2] - pad)),
+                      // e = e0 + 64 e1 + 4096 e2 tiles after it: the bytes per entry of the three power tables
+  std::vector<BsCrcStep> steps;
+};
+BsCrcPlan plan_bs_crc(const MatVecJob& job, int resident);
+// Lookup / v_perm (gf_crc.hpp): a row is `tiles` tiles of 4 KiB; every launch is grid_x = groups
+// workgroups of tpw consecutive tiles by grid_y stripes -- `per` stripes per launch (all of an affine
+// job, else 96 / (k + m), at most 65535; grid_y is the first launch's) -- workgroup g's tiles ending
+// at byte end[g] (its constant is x^(8 (len - end[g]))); dy: -1 the lookup kernel, 0 / 2 / 4 the
+// v_perm kernel's plain / 2x2 / 4x4 dyadic product.  CFSEC_CRC_GROUPS overrides the workgroup total.
+struct CrcPlan {
+  uint32_t tiles;
+  int per, dy;
+  int64_t sstride;
+  uint32_t groups, tpw, grid_x, grid_y;
+  std::vector<int64_t> end;
+};
+CrcPlan plan_matvec_crc(const MatVecJob& job, CrcRoute route, int resident);
 // shift(~0, len) ^ ~0: XOR it into a raw (zero-preset) CRC of len bytes to get crc32.ChecksumIEEE.
 uint32_t crc32_shift_ones(size_t len);
 

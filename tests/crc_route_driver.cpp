@@ -5,6 +5,7 @@
 //
 //   crc_route_driver rs:N:M ... lrc:N:M:L:AZ:PUTQUORUM ...
 //   crc_route_driver matvec rs:N:M ... lrc:... gen:K:M ...     (the plans of launch_matvec, below)
+//   crc_route_driver plan                                      (the fused launches' plans, below)
 //
 // Output, one record per line:
 //   L <len> <nst0> <nst1> <nst2>                       the lengths and the stripe counts of each
@@ -180,6 +181,104 @@ void mv_matrix(const char* tag, int k, int m, const uint8_t* coef) {
     }
 }
 
+// ---- "plan" as the first argument: the launch plans of the fused kernels (plan_bs_crc,
+// plan_matvec_crc) for tests/test_crc_plan.py, over lengths x stripe counts x layouts (aff: one stride
+// between the stripes, tab: separate allocations) x resident workgroup counts (0: the query failed).
+// Records (jobs outside the bit-sliced range print no bs record):
+//   bs <k> <m> <len> <layout> <nstripes> <resident> <resident used> <pad> <pw0> <pw1> <pw2> <runs>
+//   lk <route> <k> <m> <coef hex> <len> <layout> <nstripes> <resident> <tiles> <per> <dy> <affine> <groups> <tpw> <gx> <gy> <ends>
+// <runs>: ';'-joined "n*s0,ns,tab,affine,tps,W,groups,bend,tail,tblk,grid,jump": n consecutive launches
+// alike but for s0, which advances by ns.  <ends>: ','-joined end offsets of the workgroups.
+struct PlanRows {
+  std::vector<const uint8_t*> in;
+  std::vector<uint8_t*> out;
+};
+PlanRows plan_rows(int k, int m, uint64_t len, int nst, bool affine) {
+  PlanRows r;
+  const uint64_t base = 0x100000000000ull, pitch = (len + 255) / 256 * 256 + 256;
+  for (int s = 0; s < nst; ++s)
+    for (int i = 0; i < k + m; ++i) {
+      const uint64_t a = base + ((uint64_t)s * (k + m) + i) * pitch + (affine ? 0 : 256ull * ((s * (i + 1)) % 5));
+      if (i < k) r.in.push_back(reinterpret_cast<const uint8_t*>(a));
+      else r.out.push_back(reinterpret_cast<uint8_t*>(a));
+    }
+  return r;
+}
+
+int plans() {
+  const int kNst[] = {1, 5, 6, 7, 13, 48, 1536, 65536};
+  const int kResident[] = {1, 256, 768, 1024, 0};
+  const int kBs[][2] = {{12, 4}, {6, 12}, {3, 3}, {16, 22}, {6, 18}};
+  struct Lk { CrcRoute route; int k, m; bool enc; };  // enc: the Reed-Solomon encode rows, else a generic matrix
+  const Lk kLk[] = {{CrcRoute::kLookup, 12, 4, true}, {CrcRoute::kLookup, 6, 12, false}, {CrcRoute::kLookup, 8, 2, false},
+                    {CrcRoute::kVperm, 12, 4, true},  {CrcRoute::kVperm, 16, 4, true},   {CrcRoute::kVperm, 6, 6, true},
+                    {CrcRoute::kVperm, 6, 12, false}, {CrcRoute::kVperm, 18, 3, false},  {CrcRoute::kVperm, 8, 4, false}};
+  const auto lens = [](int k) {
+    return std::vector<uint64_t>{1, 2047, 2048, 2049, 8193, 4096ull * k - 1, 4096ull * k + 1, 699051, 5592406, 512ull << 20};
+  };
+  for (const auto& km : kBs)
+    for (uint64_t len : lens(km[0]))
+      for (int nst : kNst)
+        for (int aff = 0; aff < 2; ++aff) {
+          if ((len + 2047) / 2048 * (uint64_t)nst > 0xFFFFFFFFull) continue;
+          const PlanRows rows = plan_rows(km[0], km[1], len, nst, aff != 0);
+          MatVecJob job = make_job(km[0], km[1], nullptr, len, nst);
+          job.in = rows.in.data();
+          job.out = rows.out.data();
+          for (int res : kResident) {
+            const BsCrcPlan p = plan_bs_crc(job, res);
+            std::printf("bs %d %d %llu %s %d %d %d %lld %lld %lld %lld ", km[0], km[1], (unsigned long long)len,
+                        aff ? "aff" : "tab", nst, res, p.resident, (long long)p.pad, (long long)p.pw[0], (long long)p.pw[1],
+                        (long long)p.pw[2]);
+            for (size_t i = 0; i < p.steps.size();) {
+              const BsCrcStep& a = p.steps[i];
+              size_t n = 1;
+              for (; i + n < p.steps.size(); ++n) {
+                const BsCrcStep& b = p.steps[i + n];
+                if (b.s0 != a.s0 + (int)n * a.ns || b.ns != a.ns || b.tab != a.tab || b.sstride != a.sstride || b.tps != a.tps ||
+                    b.W != a.W || b.groups != a.groups || b.bend != a.bend || b.tail != a.tail || b.tblk != a.tblk ||
+                    b.grid != a.grid || b.jump != a.jump)
+                  break;
+              }
+              std::printf("%s%zu*%d,%d,%u,%d,%u,%u,%u,%u,%u,%u,%u,%llu", i ? ";" : "", n, a.s0, a.ns, a.tab, a.sstride != 0, a.tps,
+                          a.W, a.groups, a.bend, a.tail, a.tblk, a.grid, (unsigned long long)a.jump);
+              i += n;
+            }
+            std::printf("\n");
+          }
+        }
+  for (const Lk& c : kLk) {
+    std::vector<uint8_t> coef((size_t)c.k * c.m);
+    for (size_t i = 0; i < coef.size(); ++i) coef[i] = (uint8_t)(1 + (i * 37 + 11) % 255);
+    if (c.enc) {
+      std::unique_ptr<RSEngine> e;
+      if (RSEngine::create(c.k, c.m, -1, &e) != CFSEC_OK) return 1;
+      std::vector<bool> present(c.k + c.m, true);
+      for (int i = 0; i < c.m; ++i) present[c.k + i] = false;
+      ReconPlan plan;
+      if (e->plan_reconstruct(present, false, &plan) != CFSEC_OK || (int)plan.outputs.size() != c.m) return 2;
+      coef = plan.rows.v;
+    }
+    for (uint64_t len : lens(c.k))
+      for (int nst : kNst)
+        for (int aff = 0; aff < 2; ++aff) {
+          const PlanRows rows = plan_rows(c.k, c.m, len, nst, aff != 0);
+          MatVecJob job = make_job(c.k, c.m, coef.data(), len, nst);
+          job.in = rows.in.data();
+          job.out = rows.out.data();
+          for (int res : kResident) {
+            const CrcPlan p = plan_matvec_crc(job, c.route, res);
+            std::printf("lk %d %d %d %s %llu %s %d %d %u %d %d %d %u %u %u %u ", (int)c.route, c.k, c.m,
+                        hex(coef.data(), coef.size()).c_str(), (unsigned long long)len, aff ? "aff" : "tab", nst, res, p.tiles,
+                        p.per, p.dy, p.sstride != 0, p.groups, p.tpw, p.grid_x, p.grid_y);
+            for (size_t g = 0; g < p.end.size(); ++g) std::printf("%s%lld", g ? "," : "", (long long)p.end[g]);
+            std::printf("\n");
+          }
+        }
+  }
+  return 0;
+}
+
 int generic(int k, int m) {
   std::vector<uint8_t> coef((size_t)k * m);
   for (size_t i = 0; i < coef.size(); ++i) coef[i] = (uint8_t)(1 + (i * 37 + 11) % 255);
@@ -290,6 +389,7 @@ int lrc_mode(int N, int M, int L, int AZ, int PQ) {
 }  // namespace
 
 int main(int argc, char** argv) {
+  if (argc > 1 && !std::strcmp(argv[1], "plan")) return plans();
   g_matvec = argc > 1 && !std::strcmp(argv[1], "matvec");
   for (int li = 0; li < kNLens && !g_matvec; ++li)
     std::printf("L %llu %d %d %d\n", (unsigned long long)kLens[li], stripes(kLens[li], 0), stripes(kLens[li], 1),

@@ -81,3 +81,70 @@ def expect_plain(k, m, coef, length, nstripes, lens=False, bs_mask=BS_CRC_DEFAUL
     nets = {15: "ec6p6l9", 18: "ec6p8l10"}
     return (bool(bs_mask & PLAIN_BIT) and k == 6 and m in nets and not lens
             and b"".join(network_rows(nets[m])) == bytes(coef) and bs_in_range(length, nstripes))
+
+
+# ---- launch geometry (plan_bs_crc / plan_matvec_crc, kernels.hpp), restated from the kernels' indexing ----
+BS_WAVES = 4                  # waves of a bit-sliced workgroup
+BS_PTRS = 96                  # row pointers in its argument block
+BS_RESIDENT_FALLBACK = 768    # resident workgroups assumed when the occupancy query fails
+LK_TILE = 4096                # bytes of a row per tile of the lookup / v_perm kernels
+LK_PTRS = 96
+LK_MAX_GROUPS = 384           # group constants in their argument block
+LK_GROUPS = 1024              # workgroups per launch of the v_perm kernels (and the lookup fallback)
+
+
+def ceil_div(a, b):
+    return -(-a // b)
+
+
+def bs_plan(k, m, length, nstripes, affine, resident):
+    """The bit-sliced launches of a job: gf_bs_crc_kernel's wave (g, j) = divmod(wave id, W) walks tiles
+    j, j + W, ... < bend of stripes g, g + groups, ...; the workgroups from tblk on are tail waves, wave
+    q of them taking tile bend + q % tail of stripe q // tail.  `affine`: the stripes keep one stride
+    (a single stripe never does).  Returns (resident used, pad, power-table bytes, steps)."""
+    resident = resident if resident > 0 else BS_RESIDENT_FALLBACK
+    tps = ceil_div(length, BS_TILE)
+    per = nstripes if affine and nstripes > 1 else BS_PTRS // (k + m)
+    waves = resident * BS_WAVES
+    steps = []
+    for s0 in range(0, nstripes, per):
+        ns = min(per, nstripes - s0)
+        W = min(tps, max(1, waves // ns))      # waves per stripe: the resident waves over the stripes
+        groups = min(ns, waves // W)
+        tail = tps % W                         # the remainder tiles: one per extra wave
+        tblk = ceil_div(groups * W, BS_WAVES)
+        steps.append(dict(s0=s0, ns=ns, tab=1 if affine and nstripes > 1 else ns, affine=int(affine and nstripes > 1),
+                          tps=tps, W=W, groups=groups, bend=tps - tail, tail=tail, tblk=tblk,
+                          grid=tblk + ceil_div(tail * ns, BS_WAVES), jump=BS_TILE * W))
+    return resident, tps * BS_TILE - length, (BS_TILE, BS_TILE * 64, BS_TILE * 64 * 64), steps
+
+
+def dyadic_blocks(coef, k, m, B):
+    c = bytes(coef)
+    return all(c[(r0 + i) * k + c0 + j] == c[r0 * k + c0 + (i ^ j)]
+               for r0 in range(0, m, B) for c0 in range(0, k, B) for i in range(B) for j in range(B))
+
+
+def lk_plan(route, k, m, coef, length, nstripes, affine, resident):
+    """The lookup / v_perm launches: a (groups, stripes) grid, workgroup g taking tiles [g tpw, (g + 1)
+    tpw) of its stripe.  dy: -1 the lookup kernel; the v_perm kernel's product 4 for 4 outputs of 4x4
+    dyadic blocks (k = 12, 16), 2 for 6 x 6 of 2x2 blocks and for the 6 x 12 fused encode, else 0."""
+    affine = affine and nstripes > 1
+    tiles = ceil_div(length, LK_TILE)
+    per = min(nstripes if affine else LK_PTRS // (k + m), 65535)
+    if route == LOOKUP:
+        dy = -1
+    elif m == 12:
+        dy = 2
+    elif m == 4 and k in (12, 16) and dyadic_blocks(coef, k, m, 4):
+        dy = 4
+    elif m == 6 and k == 6 and dyadic_blocks(coef, k, m, 2):
+        dy = 2
+    else:
+        dy = 0
+    total = resident if route == LOOKUP and resident > 0 else LK_GROUPS
+    fit = min(tiles, max(1, total // min(nstripes, per)), LK_MAX_GROUPS)
+    tpw = ceil_div(tiles, fit)
+    groups = ceil_div(tiles, tpw)
+    return dict(tiles=tiles, per=per, dy=dy, affine=int(affine), groups=groups, tpw=tpw, gx=groups, gy=min(nstripes, per),
+                ends=[min((g + 1) * tpw, tiles) * LK_TILE for g in range(groups)])
