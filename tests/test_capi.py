@@ -195,6 +195,11 @@ def test_new_encoder_invalid_codemode():
         ec.NewEncoder(ec.Config(CodeMode=cm.Tactic()))
     ec.NewEncoder(ec.Config(CodeMode=cm.GetTactic(cm.EC15P12)))
     ec.NewEncoder(ec.Config(CodeMode=cm.GetTactic(cm.EC16P20L2)))
+    # any valid tactic, not only the table's code modes (tests/test_gpu_store_verify.py runs every (k, m))
+    assert (7, 5) not in {(t.N, t.M) for t in map(cm.GetTactic, cm.GetAllCodeModes())}
+    e = ec.NewEncoder(ec.Config(CodeMode=cm.Tactic(7, 5, 0, 1, 7, 0, 0)))
+    ins, rows = e.repair_rows([1, 8], [1, 8, 9])
+    assert ins == [0, 2, 3, 4, 5, 6, 7] and [len(r) for r in rows] == [7, 7, 7]
 
 
 def test_shards_in_idc_index_maps():
