@@ -44,10 +44,16 @@ Status whole_stripe_ok(const cfsec_shard* sh, int n, size_t* size) {
 // The tasks planned over the stripes a call kept (owner = index among those) belong to the items
 // pos[owner] of the call: the item's verify word, its device, and -- with crc -- the checksums of its
 // rebuilt shards (blobnode ShardCrc32) at words [item * n, item * n + n).
-void stamp_items(std::vector<StripeTask>& tasks, const std::vector<int>& pos, const CrcOut* crc, int n) {
-  for (auto& t : tasks) {
+// crc->every: every shard of the item, each word written by exactly one task -- a task checksums all
+// its rows (mode 3); where a Verify pass over the whole stripe follows a store pass (split), the
+// Verify pass alone; a task from first_local on is an AZ's local pass behind a global one, which
+// has checksummed the AZ's global shards: the local parities only (mode 4).
+void stamp_items(std::vector<StripeTask>& tasks, const std::vector<int>& pos, const CrcOut* crc, int n,
+                 size_t first_local = (size_t)-1) {
+  for (size_t i = 0; i < tasks.size(); ++i) {
+    StripeTask& t = tasks[i];
     t.owner = pos[t.owner];
-    t.crc = crc ? 1 : 0;
+    t.crc = !crc ? 0 : !crc->every ? 1 : t.split == 2 ? 0 : i >= first_local ? 4 : 3;
     t.crc_word = (int64_t)t.owner * n;
   }
 }
@@ -60,7 +66,8 @@ struct Part {
 };
 
 // The rows a task checksums: f(position in plan->in followed by plan->out, CrcOut word) for every
-// input row (crc == 2) and every stored row whose word lies in [0, nwords).
+// input row (crc == 2, 3), every stored row and every compared row (crc == 3, 4) whose word lies in
+// [0, nwords).
 template <class F>
 void for_each_crc_row(const StripeTask& t, size_t nwords, F f) {
   if (!t.crc) return;
@@ -69,9 +76,10 @@ void for_each_crc_row(const StripeTask& t, size_t nwords, F f) {
     const int64_t w = t.crc_word + (t.crc_map ? t.crc_map[row] : row);
     if (w >= 0 && (size_t)w < nwords) f(p, (size_t)w);
   };
-  if (t.crc == 2)
+  if (t.crc == 2 || t.crc == 3)
     for (size_t c = 0; c < k; ++c) visit(c, t.plan->in[c]);
-  for (int r = 0; r < t.plan->nstore; ++r) visit(k + r, t.plan->out[r]);
+  const size_t nout = t.crc >= 3 ? t.plan->out.size() : (size_t)t.plan->nstore;
+  for (size_t r = 0; r < nout; ++r) visit(k + r, t.plan->out[r]);
 }
 
 // Rows of one device launch group: stripes sharing a plan.
@@ -190,8 +198,11 @@ int64_t crc_word_stride(const Group& g, int mode, int maxrow, size_t nwords,
 // that reads every row again (EC12P4 8 x 64 MiB: 130 + 123 us -> ~180 us).  Returns false when the
 // group does not qualify (then the product and the separate pass run as before).  The words are
 // zeroed by run_device already (the launch skips its own memset).
+// A group that compares rows too (nstore < m: Reconstruct + Verify) qualifies when its tasks checksum
+// every row (mode 3) and the route takes the kStoreVerify job; its Verify words are routed as
+// launch_group_run routes them.  Mode 3 with nothing compared is the mode-2 launch.
 bool fused_crc_group(const Group& g, uint32_t* dcrc, size_t nwords, const std::map<int, int>& tasks_per_owner,
-                     hipStream_t s, Status* st) {
+                     uint32_t* dflags, hipStream_t s, Status* st) {
   static const bool kOn = [] {  // CFSEC_BATCH_FUSED_CRC=0: the separate pass always (A/B)
     const char* v = std::getenv("CFSEC_BATCH_FUSED_CRC");
     return !(v && v[0] == '0');
@@ -199,21 +210,28 @@ bool fused_crc_group(const Group& g, uint32_t* dcrc, size_t nwords, const std::m
   const StripePlan& p = *g.plan;
   const int k = (int)p.in.size(), m = (int)p.out.size();
   const size_t nt = g.tasks.size();
-  if (!kOn || p.dy16 || p.nstore != m || m == 0 || nt == 0) return false;
+  const bool sv = p.nstore != m;
+  if (!kOn || p.dy16 || m == 0 || nt == 0) return false;
   const uint64_t len = g.lens[0];
   if (len == 0) return false;
   const StripeTask* t0 = g.tasks[0];
   const int mode = t0->crc;  // 2: inputs and outputs, 1: the stored outputs only
-  if (mode == 0) return false;  // mode rule: any checksum mode, the one the tasks share
+  if (mode == 0 || mode == 4) return false;  // mode rule: any checksum mode, the one the tasks share
+  if (sv && (mode != 3 || p.nstore == 0)) return false;
   int maxrow = 0;
   for (int c : p.in) maxrow = std::max(maxrow, c);
   for (int o : p.out) maxrow = std::max(maxrow, o);
   const int64_t cs = crc_word_stride(g, mode, maxrow, nwords, tasks_per_owner);
   if (cs == 0 || cs > 256) return false;  // no fused route takes a stride past 256 words (kernels.hpp)
   std::vector<int> slot(k + m);
-  for (int c = 0; c < k; ++c) slot[c] = mode == 2 ? p.in[c] : -1;
+  for (int c = 0; c < k; ++c) slot[c] = mode >= 2 ? p.in[c] : -1;
   for (int r = 0; r < m; ++r) slot[k + r] = p.out[r];
-  const MatVecJob job = matvec_job(k, m, p.rows.v.data(), len, (int)nt, g.in.data(), g.out.data());
+  MatVecJob job = matvec_job(k, m, p.rows.v.data(), len, (int)nt, g.in.data(), g.out.data());
+  if (sv) {
+    job.mode = MatVecMode::kStoreVerify;
+    job.nstore = p.nstore;
+    job.flags = g.direct ? g.direct : dflags + g.flag0;
+  }
   // the route of exactly this job (its slots, length and stripe count): a shape only the bit-sliced
   // kernel covers has one with every shard checksummed (mode 2) and the tile counts in range only
   if (!matvec_crc_accepts(job, (int)cs, slot.data())) return false;
@@ -627,9 +645,13 @@ void RSEngine::plan_reconstruct_tasks(cfsec_shard* const* stripes, int nst, bool
       if (!vplan) vplan = store->add(whole_stripe_plan(k_, total(), parity_, 0));
       use = so;
       StripeTask vt{sh, vplan, S, &status[s], 0, phase + 1, owner0 + s};
+      vt.split = 1;
       tasks->push_back(vt);
     }
-    if (!use->out.empty()) tasks->push_back(StripeTask{sh, use, S, &status[s], 0, phase, owner0 + s});
+    if (!use->out.empty()) {
+      tasks->push_back(StripeTask{sh, use, S, &status[s], 0, phase, owner0 + s});
+      tasks->back().split = use != plan ? 2 : 0;
+    }
   }
 }
 
@@ -959,7 +981,7 @@ Status BatchRun::launch_part(const Part& part, hipStream_t s, bool fuse_crc) {
   std::vector<char> taken(part.tasks.size(), 0);  // tasks whose checksums a launch took
   for (const Group& gr : groups) {
     if (st != CFSEC_OK) break;
-    if (fuse_crc && fused_crc_group(gr, dcrc, crc->n, tasks_per_owner, s, &st)) {
+    if (fuse_crc && fused_crc_group(gr, dcrc, crc->n, tasks_per_owner, ws->bflags, s, &st)) {
       for (size_t i : gr.at) taken[i] = 1;
       continue;
     }
@@ -1077,10 +1099,12 @@ namespace {
 // Synchronous calls return checksums only for the items that succeeded (the reference checksums
 // after a successful Encode / repair): the words of a failed item are zeroed.  (Asynchronous calls
 // learn a false Verify on the stream; their caller skips the words of flagged items.)
+// The repair form (crc->every) keeps the words of a bid whose Verify is false: they are the
+// checksums of what is in memory, the survivors' check among them.
 void clear_failed_crcs(const CrcOut* crc, const AsyncOut* async, const int* status, int nitems, int n) {
   if (!crc || async) return;
   for (int b = 0; b < nitems; ++b)
-    if (status[b] != CFSEC_OK)
+    if (status[b] != CFSEC_OK && !(crc->every && status[b] == CFSEC_ERR_VERIFY))
       for (int i = 0; i < n && (size_t)b * n + i < crc->n; ++i) crc->words[(size_t)b * n + i] = 0;
 }
 }  // namespace
@@ -1284,7 +1308,8 @@ Status LrcEncoder::reconstruct_batch(cfsec_shard* shards, int n, int nbids, cons
     tasks[t].crc_map = idc[vaz[v]].data();  // local index -> global shard index
   }
   ph.reset();
-  stamp_items(tasks, pos, crc, n);  // the bid: its device, its verify word; rebuilt shards, global or local
+  // the bid: its device, its verify word; rebuilt shards, global or local
+  stamp_items(tasks, pos, crc, n, first_local);
   const Status rc = engine_->run_stripes(tasks, mem, async, crc);
   // per bid: a Reconstruct error (global, then local) wins over a failed Verify
   std::vector<int> local_err(stripes.size(), CFSEC_OK);

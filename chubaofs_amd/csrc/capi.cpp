@@ -173,7 +173,7 @@ int crc32block_call(bool encode, const uint8_t* src, int64_t src_len, int64_t si
 
 extern "C" {
 
-const char* cfsec_version(void) { return "cfsec 0.4.0 (gfx950)"; }
+const char* cfsec_version(void) { return "cfsec 0.5.0 (gfx950)"; }
 
 const char* cfsec_last_error(void) { return cfsec::last_error_cstr(); }
 
@@ -315,6 +315,15 @@ int cfsec_rs_reconstruct_crc_batch(cfsec_rs* h, uint8_t* const* ptrs, size_t sha
   });
 }
 
+int cfsec_rs_repair_crc_batch(cfsec_rs* h, uint8_t* const* ptrs, size_t shard_size, int nstripes,
+                              const int* erased, int nerased, uint32_t* flags, uint32_t* crcs, void* stream) {
+  if (!h || nstripes < 0 || nerased < 0 || (nstripes > 0 && (!ptrs || !flags || !crcs)) || (nerased > 0 && !erased))
+    return CFSEC_ERR_INVALID_ARG;
+  return guarded([&] {
+    return h->e->repair_crc_batch(ptrs, shard_size, nstripes, erased, nerased, flags, crcs, as_stream(stream));
+  });
+}
+
 // ---------------- stripe batches ----------------
 
 int cfsec_rs_set_devices(cfsec_rs* h, const int* devices, int ndev) {
@@ -453,6 +462,37 @@ int cfsec_ec_reconstruct_batch_crc(cfsec_ec* h, cfsec_shard* shards, int n, int 
   return guarded([&] {
     return h->e->reconstruct_batch(shards, n, nbids, bad_idx, bad_off, mem, verify != 0, status, nullptr, &c);
   });
+}
+
+int cfsec_ec_repair_batch_crc(cfsec_ec* h, cfsec_shard* shards, int n, int nbids, const int* bad_idx,
+                              const int* bad_off, int mem, int* status, uint32_t* crcs, const uint32_t* expect,
+                              int* mismatch) {
+  if (!h || nbids < 0 || n <= 0 || (nbids > 0 && (!shards || !status || !bad_off || !crcs)) || (expect && !mismatch))
+    return CFSEC_ERR_INVALID_ARG;
+  if (nbids > 0 && bad_off[0] != 0) return CFSEC_ERR_INVALID_ARG;
+  for (int b = 0; b < nbids; ++b) {
+    if (bad_off[b + 1] < bad_off[b] || (bad_off[b + 1] > bad_off[b] && !bad_idx)) return CFSEC_ERR_INVALID_ARG;
+    if (mismatch) mismatch[b] = -1;
+  }
+  std::memset(crcs, 0, sizeof(uint32_t) * (size_t)nbids * n);
+  cfsec::CrcOut c;
+  c.words = crcs;
+  c.n = (size_t)nbids * n;
+  c.every = true;
+  const int rc = guarded([&] {
+    return h->e->reconstruct_batch(shards, n, nbids, bad_idx, bad_off, mem, true, status, nullptr, &c);
+  });
+  if (rc != CFSEC_OK || !expect) return rc;
+  // downloadShard's check (work_shard_recover.go:654-685) on the words that came back: host arithmetic
+  for (int b = 0; b < nbids; ++b) {
+    if (status[b] != CFSEC_OK && status[b] != CFSEC_ERR_VERIFY) continue;
+    for (int i = 0; i < n && mismatch[b] < 0; ++i) {
+      bool bad = false;
+      for (int j = bad_off[b]; j < bad_off[b + 1]; ++j) bad = bad || bad_idx[j] == i;
+      if (!bad && crcs[(size_t)b * n + i] != expect[(size_t)b * n + i]) mismatch[b] = i;
+    }
+  }
+  return rc;
 }
 
 int cfsec_ec_encode_batch_crc(cfsec_ec* h, cfsec_shard* shards, int n, int nstripes, int mem, int* status,

@@ -1121,6 +1121,47 @@ Status RSEngine::reconstruct_crc_batch(uint8_t* const* ptrs, size_t S, int nstri
   return matvec_with_crc(job, ptrs, total(), slot, S, crcs, stream);
 }
 
+Status RSEngine::repair_crc_batch(uint8_t* const* ptrs, size_t S, int nstripes, const int* erased, int nerased,
+                                  uint32_t* flags, uint32_t* crcs, hipStream_t stream) {
+  if (!ptrs || !crcs || !flags || nstripes < 0 || nerased < 0 || (nerased > 0 && !erased))
+    return CFSEC_ERR_INVALID_ARG;
+  std::vector<bool> present;
+  if (!parse_erased(erased, nerased, total(), &present)) return CFSEC_ERR_INVALID_ARG;
+  if (!ctx_) return CFSEC_ERR_DEVICE;
+  int np = 0;
+  for (int i = 0; i < total(); ++i) np += present[i] ? 1 : 0;
+  if (np < k_ && nstripes > 0) return CFSEC_ERR_TOO_FEW_SHARDS;
+  if (k_ > kLaunchMaxRows) return CFSEC_ERR_NOT_SUPPORTED;  // compared rows over more inputs than a launch carries
+  DeviceGuard g(ctx_->device());
+  if (!g.ok()) return hip_status(hipErrorInvalidDevice, "hipSetDevice");
+  if (nstripes == 0) return CFSEC_OK;
+  if (S == 0) return hip_status(hipMemsetAsync(crcs, 0, 4 * (size_t)total() * nstripes, stream), "hipMemsetAsync");
+  // the batch layer's plan of a bid: the first k present shards in, the missing ones stored, every
+  // other present parity shard compared -- each shard exactly once
+  StripePlan plan;
+  const Status st = plan_stripe(present, true, &plan, nullptr);
+  if (st != CFSEC_OK) return st;
+  const int nout = (int)plan.out.size();
+  if (nout > kLaunchMaxRows && plan.nstore > 0 && plan.nstore < nout) return CFSEC_ERR_NOT_SUPPORTED;
+  if (nout == 0) {  // no parity shards: nothing to rebuild or compare
+    Status z = hip_status(hipMemsetAsync(crcs, 0, 4 * (size_t)total() * nstripes, stream), "hipMemsetAsync");
+    if (z != CFSEC_OK) return z;
+    std::vector<const uint8_t*> p(ptrs, ptrs + (size_t)total() * nstripes);
+    return hip_status(launch_crc32_to(p.data(), S, (int)p.size(), crcs, nullptr, crc32_shift_ones(S), stream),
+                      "launch_crc32_to");
+  }
+  const PtrTables t = ptr_tables(ptrs, total(), nstripes, plan.in, plan.out);
+  MatVecJob job = matvec_job(k_, nout, plan.rows.v.data(), S, nstripes, t.in.data(), t.out.data());
+  if (plan.nstore < nout) {
+    job.mode = MatVecMode::kStoreVerify;
+    job.nstore = plan.nstore;
+    job.flags = flags;
+  }
+  std::vector<int> slot(plan.in);
+  slot.insert(slot.end(), plan.out.begin(), plan.out.end());
+  return matvec_with_crc(job, ptrs, total(), slot, S, crcs, stream);
+}
+
 // ---------------------------------------------------------------- ec.Encoder
 
 Status ECEncoder::create(const cfsec_tactic& t, bool enable_verify, int concurrency, int device,

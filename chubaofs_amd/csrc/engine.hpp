@@ -233,6 +233,10 @@ struct AsyncOut {
 struct CrcOut {
   uint32_t* words = nullptr;
   size_t n = 0;
+  // reconstruct batches: false = the shards the call rebuilt (the _crc forms), true = every shard of
+  // the bid as it stands after the call, survivors included (the repair form: StripeTask::crc = 3),
+  // kept for a bid whose Verify is false
+  bool every = false;
 };
 
 // One stripe of a batch call: its shard vector, the plan, its length, its result.
@@ -245,9 +249,13 @@ struct StripeTask {
   int phase = 0;                // tasks of phase p run after every task of phase p - 1 (same call)
   int owner = 0;                // batch item: a host batch keeps an item's tasks on one device; the
                                 // item's Verify word (asynchronous calls: the caller's flags[owner])
-  int crc = 0;                  // checksums: 0 none, 1 the stored rows, 2 every row (inputs + stored)
+  int crc = 0;                  // checksums: 0 none, 1 the stored rows, 2 inputs + stored rows, 3 every row
+                                // (inputs, stored and compared rows, ExtraRows included), 4 the stored and
+                                // compared rows (an AZ's local pass of a bid whose global pass is in mode 3:
+                                // every word of an item is written by exactly one task)
   int64_t crc_word = 0;         // CrcOut word of shard index 0 of this task's item
   const int* crc_map = nullptr; // shard index -> index in the item (local views), or identity
+  int split = 0;                // CFSEC_VERIFY_SPLIT: 1 the Verify pass over the whole stripe, 2 its store pass
 };
 
 // The stripe ranges [t0, t1) one launch group (stripes sharing a plan) is launched in, by the
@@ -314,6 +322,10 @@ class RSEngine {
   Status encode_crc_batch(uint8_t* const* ptrs, size_t S, int nstripes, uint32_t* crcs, hipStream_t stream);
   Status reconstruct_crc_batch(uint8_t* const* ptrs, size_t S, int nstripes, const int* erased, int nerased,
                                bool data_only, uint32_t* crcs, hipStream_t stream);
+  // Reconstruct, the Verify of the same pass (flags[s] |= 1 on a mismatch, as verify_batch) and every
+  // shard's checksum as it stands afterwards: every word of crcs filled.
+  Status repair_crc_batch(uint8_t* const* ptrs, size_t S, int nstripes, const int* erased, int nerased,
+                          uint32_t* flags, uint32_t* crcs, hipStream_t stream);
 
   // Plan the rows of a reconstruct given which shards are present.
   Status plan_reconstruct(const std::vector<bool>& present, bool data_only, ReconPlan* plan);

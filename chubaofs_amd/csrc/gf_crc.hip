@@ -16,6 +16,11 @@ CFSEC_CRC_EXTERN(8)
 CFSEC_CRC_EXTERN(12)
 CFSEC_CRC_EXTERN(16)
 CFSEC_CRC_EXTERN(18)
+CFSEC_CRC_SV_EXTERN(6)
+CFSEC_CRC_SV_EXTERN(8)
+CFSEC_CRC_SV_EXTERN(12)
+CFSEC_CRC_SV_EXTERN(16)
+CFSEC_CRC_SV_EXTERN(18)
 }  // namespace crcdev
 
 namespace {
@@ -168,6 +173,17 @@ hipError_t launch_crc(int k, int m, const GfCrcArgs& a, dim3 grid, hipStream_t s
   }
 }
 
+hipError_t launch_crc_sv(int k, int m, const GfCrcArgs& a, dim3 grid, hipStream_t st) {
+  switch (k) {
+    case 6: return crcdev::launch_crc_sv_k<6>(m, a, grid, st);
+    case 8: return crcdev::launch_crc_sv_k<8>(m, a, grid, st);
+    case 12: return crcdev::launch_crc_sv_k<12>(m, a, grid, st);
+    case 16: return crcdev::launch_crc_sv_k<16>(m, a, grid, st);
+    case 18: return crcdev::launch_crc_sv_k<18>(m, a, grid, st);
+    default: return hipErrorInvalidValue;
+  }
+}
+
 }  // namespace
 
 // The lookup-product fused kernel (gf_crc_lds_kernel): m <= 4, k <= 16, and (round 6) k = 6, m = 12 --
@@ -182,17 +198,33 @@ static bool crc_lds12_on() {
   return v;
 }
 
+// Reconstruct + Verify with every row checksummed (gf_crc_sv_kernel); CFSEC_SV_CRC=0 sends those jobs
+// to the product and the separate pass (A/B).
+static bool crc_sv_on() {
+  static const bool v = env_u32("CFSEC_SV_CRC", 1) != 0;
+  return v;
+}
+
 // The one routing decision of the fused product + checksum kernels (kernels.hpp): host arithmetic on
 // the job's scalars, coef, slot and the masks above, no HIP calls.
 CrcRoute matvec_crc_route(const MatVecJob& job, int crc_stride, const int* slot) {
   const int k = job.k, m = job.m;
-  if (job.mode != MatVecMode::kStore || k < 1 || m < 1 || job.len > 0xFFFFFFFFull - crcdev::kTile || !slot ||
+  const bool sv = job.mode == MatVecMode::kStoreVerify;
+  if ((job.mode != MatVecMode::kStore && !sv) || k < 1 || m < 1 || job.len > 0xFFFFFFFFull - crcdev::kTile || !slot ||
       crc_stride <= 0 || crc_stride > 256 || job.nstripes < 0 || !job.coef || !job.in || !job.out)
     return CrcRoute::kNone;
   const bool cin = slot[0] >= 0;
   for (int i = 0; i < k + m; ++i) {
     const bool want = i >= k || cin;
     if (want && (slot[i] < 0 || slot[i] >= crc_stride)) return CrcRoute::kNone;
+  }
+  // Reconstruct + Verify (kStoreVerify): the v_perm kernel gf_crc_sv_kernel alone -- a stored and a
+  // compared row at least, every row checksummed, one length, the Verify words given
+  if (sv) {
+    const bool shape = (k == 6 || k == 8 || k == 12 || k == 16 || k == 18) && m >= 2 && m <= 6;
+    return crc_sv_on() && shape && job.nstore > 0 && job.nstore < m && cin && !job.lens && job.flags
+               ? CrcRoute::kVperm
+               : CrcRoute::kNone;
   }
   // a code mode's bit-sliced network, checksums from its bit planes (gf_bs_crc.hip): only with the
   // inputs checksummed and the tile counts in its range -- a shape nothing else covers (k = 3, 4, 10,
@@ -239,6 +271,8 @@ CrcPlan plan_matvec_crc(const MatVecJob& job, CrcRoute route, int resident) {
   // 6 x 12 is EC6P10L2's fused encode + its 18 checksums (the route: that form, inputs checksummed)
   if (route == CrcRoute::kLookup) {
     p.dy = -1;
+  } else if (job.mode == MatVecMode::kStoreVerify) {
+    p.dy = 0;  // decode rows: the plain product
   } else if (m == 12) {
     p.dy = 2;
   } else if ((m == 4 && k % 4 == 0) || (k == 6 && m == 6)) {
@@ -273,7 +307,9 @@ hipError_t launch_matvec_crc(const MatVecJob& job, uint32_t* crc, int crc_stride
   if (route == CrcRoute::kNone) return hipErrorInvalidValue;
   const int k = job.k, m = job.m;
   const bool cin = slot[0] >= 0;
-  if (env_u32("CFSEC_TRACE_CRC", 0))  // read per call: tests turn it on mid-process
+  const bool sv = job.mode == MatVecMode::kStoreVerify;
+  const bool trace = env_u32("CFSEC_TRACE_CRC", 0) != 0;  // read per call: tests turn it on mid-process
+  if (trace && !sv)
     std::fprintf(stderr, "cfsec: crc route=%s k=%d m=%d cin=%d stripes=%d len=%llu\n", crc_route_name(route), k, m,
                  (int)cin, job.nstripes, (unsigned long long)job.len);
   hipError_t e = zero ? hipMemsetAsync(crc, 0, sizeof(uint32_t) * (size_t)crc_stride * job.nstripes, stream)
@@ -293,6 +329,10 @@ hipError_t launch_matvec_crc(const MatVecJob& job, uint32_t* crc, int crc_stride
       resident = per_cu * cus;
   }
   const CrcPlan p = plan_matvec_crc(job, route, resident);
+  if (trace && sv)
+    std::fprintf(stderr, "cfsec: crc sv k=%d m=%d nstore=%d stripes=%d len=%llu tpw=%u groups=%u per=%d\n", k, m,
+                 job.nstore, job.nstripes, (unsigned long long)job.len, p.tpw, p.groups, p.per);
+  a.nstore = sv ? (uint32_t)job.nstore : 0u;
   for (int r = 0; r < m; ++r)
     for (int c = 0; c < k; ++c) a.coef[r * k + c] = job.coef[(size_t)r * k + c];
   a.len = job.len;
@@ -315,6 +355,12 @@ hipError_t launch_matvec_crc(const MatVecJob& job, uint32_t* crc, int crc_stride
       for (int r = 0; r < m; ++r) a.ptr[tab * k + s * m + r] = job.out[(size_t)(s0 + s) * m + r];
     }
     const dim3 grid(p.grid_x, (unsigned)ns);
+    if (sv) {
+      a.flags = job.flags + s0;
+      e = launch_crc_sv(k, m, a, grid, stream);
+      if (e != hipSuccess) return e;
+      continue;
+    }
     e = cin ? launch_crc<true>(k, m, a, grid, stream, p.dy) : launch_crc<false>(k, m, a, grid, stream, p.dy);
     if (e != hipSuccess) return e;
   }

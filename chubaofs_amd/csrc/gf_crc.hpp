@@ -56,7 +56,8 @@ struct __attribute__((aligned(16))) GfCrcArgs {
   uint32_t tab, fin;     // stripes held in ptr[]; shift(~0, len) ^ ~0
   uint32_t* crc;         // [stripe][crc_stride] checksum words, zeroed by the launcher
   const uint32_t* tabs;  // the device table block
-  uint32_t crc_stride, pad0;
+  uint32_t* flags;       // kStoreVerify (gf_crc_sv_kernel): the launch's Verify words, one per stripe
+  uint32_t crc_stride, nstore;  // nstore: kStoreVerify: rows [0, nstore) stored, [nstore, m) compared
   uint8_t slot[kMaxK + kMaxM];  // checksum word of kernel row i (inputs 0..k-1, outputs k..)
   uint8_t coef[kMaxM * kMaxK];
   const uint8_t* ptr[kPtrSlots];  // [tab*k inputs][tab*m outputs], as GfArgs
@@ -386,6 +387,185 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(DY ? 3 : 4,
     pre = next && (uint64_t)off + dev::kLaneBytes <= a.len;
   }
   crc_epilogue<K, NR, CIN>(a, R, red, g, stripe, threadIdx.x);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Reconstruct + Verify with every row checksummed (MatVecMode::kStoreVerify): blobnode's repair of a
+// bid checks each downloaded survivor's CRC32 (work_shard_recover.go:654-685), runs Reconstruct then
+// Verify (:751-760) and checksums each rebuilt shard (:335-342).  The product of this pass reads every
+// present shard of the bid anyway -- the first K as inputs, the rest as compared rows -- so all K + M
+// checksums come out of it: crc_tile above with rows [nstore, M) loaded and compared instead of
+// stored, their Horner registers fed from the loaded bytes (the word is the checksum of what is in
+// memory, whatever Verify says).  nstore is a launch argument (0 < nstore < M), one wave-uniform
+// branch per row as in the fixed-K kStoreVerify kernels (a compile-time row split would
+// multiply the instantiations by M).  The compared rows' pieces are loaded one column pair before the
+// end of the product.  The plain v_perm product only: decode rows are general matrices.
+template <int K, int M>
+__device__ __forceinline__ void crc_tile_sv(const GfCrcArgs& a, size_t ts, int64_t sbase, int nstore,
+                                            const u32x4* tab01, const uint32_t* tab2, const uint32_t* ct,
+                                            const uint8_t* const (&row)[K + M], uint32_t off,
+                                            bool pre, bool next, uint32_t (&x)[K][4], uint32_t (&R)[K + M],
+                                            uint32_t& diff) {
+  constexpr int D = 2 < K ? 2 : K;       // input rows loaded ahead of the product
+  constexpr int CY = K >= 4 ? K - 4 : 0;  // the column pair before which the compared rows are loaded
+  static_assert(K % 2 == 0 && D % 2 == 0 && M >= 2, "row pairs; a stored and a compared row");
+  uint32_t acc[M][4], y[M][4];  // y[r]: compared row r as loaded (row 0 is always stored)
+#pragma unroll
+  for (int r = 0; r < M; ++r)
+#pragma unroll
+    for (int w = 0; w < 4; ++w) acc[r][w] = y[r][w] = 0u;
+  const auto pin = [&]() {
+#pragma unroll
+    for (int r = 0; r < M; ++r)
+      asm volatile("" : "+v"(acc[r][0]), "+v"(acc[r][1]), "+v"(acc[r][2]), "+v"(acc[r][3]));
+  };
+  const uint64_t len = a.len;
+  const bool full = (uint64_t)off + dev::kLaneBytes <= len;
+  const size_t rem = full ? dev::kLaneBytes : off < len ? (size_t)(len - off) : 0;
+  if (full) {
+    const auto load = [&](int c, uint32_t o) {
+      const u32x4 v = dev::ld16<true>(row[c] + o);
+      x[c][0] = v.x;
+      x[c][1] = v.y;
+      x[c][2] = v.z;
+      x[c][3] = v.w;
+    };
+    if (!pre)
+#pragma unroll
+      for (int c = 0; c < D; ++c) load(c, off);
+#pragma unroll
+    for (int c = 0; c < K; c += 2) {
+#pragma unroll
+      for (int j = c + D; j < c + D + 2; ++j) {
+        if (j < K) load(j, off);
+        else if (next) load(j - K, off + kTile);
+      }
+      if (c == CY) {
+#pragma unroll
+        for (int r = 1; r < M; ++r)
+          if (r >= nstore) {
+            const u32x4 v = dev::ld16<true>(row[K + r] + off);
+            y[r][0] = v.x;
+            y[r][1] = v.y;
+            y[r][2] = v.z;
+            y[r][3] = v.w;
+          }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      dev::mac_pair_k<M>(acc, x[c], x[c + 1], tab01 + c * M, tab2 + c * M, tab01 + (c + 1) * M,
+                         tab2 + (c + 1) * M);
+      pin();
+      R[c] = crc_step5(ct, R[c], x[c]);
+      R[c + 1] = crc_step5(ct, R[c + 1], x[c + 1]);
+      asm volatile("" : "+v"(R[c]), "+v"(R[c + 1]));
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  } else {
+    // a rolled loop (unrolled, its K byte-granular loads are all hoisted: 1-4 KiB of scratch per lane);
+    // the row pointer comes from the argument block, so row[] stays in registers
+#pragma nounroll
+    for (int c = 0; c < K; ++c) {
+      uint32_t xv[4] = {0u, 0u, 0u, 0u};
+      if (rem) {
+        const u32x4 v = dev::ld_tail_row(a.ptr[ts * K + c] + sbase + off, rem, len);
+        xv[0] = v.x;
+        xv[1] = v.y;
+        xv[2] = v.z;
+        xv[3] = v.w;
+      }
+      dev::mac_row_k<M>(acc, xv, tab01 + c * M, tab2 + c * M);
+      R[c] = crc_step5(ct, R[c], xv);
+    }
+    if (rem)
+#pragma unroll
+      for (int r = 1; r < M; ++r)
+        if (r >= nstore) {  // bytes < len only, zero above: as the inputs
+          const u32x4 v = dev::ld_tail_row(row[K + r] + off, rem, len);
+          y[r][0] = v.x;
+          y[r][1] = v.y;
+          y[r][2] = v.z;
+          y[r][3] = v.w;
+        }
+  }
+  // stored rows: acc goes out and into the row's register; compared rows: the loaded piece against
+  // acc (zero-padded alike past the row's end) and into the register
+#pragma unroll
+  for (int r = 0; r < M; ++r) {
+    uint32_t d[4];
+    if (r == 0 || r < nstore) {
+      uint8_t* p = const_cast<uint8_t*>(row[K + r]) + off;
+      const u32x4 v{acc[r][0], acc[r][1], acc[r][2], acc[r][3]};
+      if (full) dev::st16_out<true>(p, v);
+      else if (rem) dev::st_tail(p, v, rem);
+#pragma unroll
+      for (int w = 0; w < 4; ++w) d[w] = acc[r][w];
+    } else {
+#pragma unroll
+      for (int w = 0; w < 4; ++w) {
+        diff |= acc[r][w] ^ y[r][w];
+        d[w] = y[r][w];
+      }
+    }
+    R[K + r] = crc_step5(ct, R[K + r], d);
+  }
+}
+
+// Waves per SIMD the register allocation aims at: the most at which no instantiation uses scratch
+// (profiles/r07/sv_crc_resources.txt): K + M Horner registers, M accumulators and M - 1 loaded rows.
+constexpr int sv_waves(int K, int M) { return M <= 2 ? 4 : K == 6 && M >= 5 ? 2 : 3; }
+
+template <int K, int M>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sv_waves(K, M), 8))) void gf_crc_sv_kernel(const GfCrcArgs a) {
+  constexpr int NR = K + M;  // every row is checksummed
+  __shared__ u32x4 tab01[K * M];
+  __shared__ uint32_t tab2[K * M];
+  __shared__ uint32_t ct[kFiveTabWords];
+  __shared__ uint32_t red[4][NR];
+  dev::build_tables<M>(K, M, a.coef, tab01, tab2);
+  for (int i = threadIdx.x; i < kFiveTabWords; i += 256) ct[i] = a.tabs[kFiveTabBase + i];
+  __syncthreads();
+
+  const uint32_t g = blockIdx.x, stripe = blockIdx.y;
+  const size_t ts = a.sstride ? 0 : (size_t)stripe;
+  const int64_t sbase = (int64_t)stripe * a.sstride;
+  const uint8_t* row[K + M];
+#pragma unroll
+  for (int c = 0; c < K; ++c) row[c] = a.ptr[ts * K + c] + sbase;
+#pragma unroll
+  for (int r = 0; r < M; ++r) row[K + r] = a.ptr[(size_t)a.tab * K + ts * M + r] + sbase;
+  uint32_t R[NR];
+#pragma unroll
+  for (int i = 0; i < NR; ++i) R[i] = 0u;
+  const uint32_t t0 = g * a.tpw;
+  const uint32_t t1 = min(t0 + a.tpw, a.tiles);
+  const uint32_t lanepos = threadIdx.x * dev::kLaneBytes;
+  const int nstore = (int)a.nstore;
+  uint32_t x[K][4];
+  uint32_t diff = 0u;
+  bool pre = false;
+  for (uint32_t t = t0; t < t1; ++t) {
+    const uint32_t off = t * kTile + lanepos;
+    const bool next = t + 1 < t1 && (uint64_t)off + kTile + dev::kLaneBytes <= a.len;
+    crc_tile_sv<K, M>(a, ts, sbase, nstore, tab01, tab2, ct, row, off, pre, next, x, R, diff);
+    pre = next && (uint64_t)off + dev::kLaneBytes <= a.len;
+  }
+  if (diff) dev::set_flag(a.flags, stripe);
+  crc_epilogue<K, NR, true>(a, R, red, g, stripe, threadIdx.x);
+}
+
+// Launch gf_crc_sv_kernel<K, m> (instantiated for m = 2..6 in gf_crc_sv_k<K>.hip).
+template <int K>
+hipError_t launch_crc_sv_k(int m, const GfCrcArgs& a, dim3 grid, hipStream_t st) {
+  switch (m) {
+#define CFSEC_CRC_SV_CASE(MV)                                                       \
+  case MV:                                                                          \
+    hipLaunchKernelGGL((gf_crc_sv_kernel<K, MV>), grid, dim3(256), 0, st, a); \
+    break;
+    CFSEC_CRC_SV_CASE(2) CFSEC_CRC_SV_CASE(3) CFSEC_CRC_SV_CASE(4) CFSEC_CRC_SV_CASE(5) CFSEC_CRC_SV_CASE(6)
+#undef CFSEC_CRC_SV_CASE
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -807,6 +987,8 @@ int lds_blocks_per_cu(int m) {
   extern template hipError_t launch_crc_k<K, false>(int, const GfCrcArgs&, dim3, hipStream_t, int); \
   extern template int lds_blocks_per_cu<K, true>(int);                                              \
   extern template int lds_blocks_per_cu<K, false>(int);
+#define CFSEC_CRC_SV_EXTERN(K) \
+  extern template hipError_t launch_crc_sv_k<K>(int, const GfCrcArgs&, dim3, hipStream_t);
 
 }  // namespace crcdev
 }  // namespace cfsec
@@ -819,4 +1001,11 @@ int lds_blocks_per_cu(int m) {
   template int lds_blocks_per_cu<K, true>(int);                                                      \
   template int lds_blocks_per_cu<K, false>(int);                                                     \
   }                                                                                                  \
+  }
+
+#define CFSEC_CRC_SV_INSTANTIATE(K)                                                        \
+  namespace cfsec {                                                                        \
+  namespace crcdev {                                                                       \
+  template hipError_t launch_crc_sv_k<K>(int, const GfCrcArgs&, dim3, hipStream_t);        \
+  }                                                                                        \
   }

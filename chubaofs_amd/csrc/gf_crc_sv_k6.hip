@@ -1,0 +1,4 @@
+// gf_crc_sv_k6.hip -- Reconstruct + Verify with every row checksummed (gf_crc_sv_kernel), k = 6; see gf_crc.hpp.
+#include "gf_crc.hpp"
+
+CFSEC_CRC_SV_INSTANTIATE(6)

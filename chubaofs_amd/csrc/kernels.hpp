@@ -142,7 +142,7 @@ uint32_t crc32_finalize(uint32_t raw, size_t len);
 hipError_t launch_crc32_to(const uint8_t* const* ptrs, size_t len, int n, uint32_t* out, const uint32_t* idx,
                            uint32_t fin, hipStream_t stream);
 
-// Encode / reconstruct (kStore) with crc32.ChecksumIEEE of the rows the product touches, fused
+// Encode / reconstruct (kStore) and Reconstruct + Verify (kStoreVerify) with crc32.ChecksumIEEE of the rows the product touches, fused
 // into the product kernel (gf_crc.hpp): row i of the product (inputs 0..k-1, then outputs) has its
 // checksum in device word crc[s * crc_stride + slot[i]] of stripe s.  slot[0] < 0 skips the inputs
 // (checksum the outputs only).  Every word of crc[0 .. nstripes*crc_stride) is zeroed first, so
@@ -150,23 +150,30 @@ hipError_t launch_crc32_to(const uint8_t* const* ptrs, size_t len, int n, uint32
 //
 // Which fused kernel runs a job, decided in one place (gf_crc.hip).  A pure host function: no HIP
 // calls, it reads the job's scalar fields, coef, slot and the A/B masks (CFSEC_BS_CRC,
-// CFSEC_CRC_LDS, CFSEC_CRC_LDS12):
+// CFSEC_CRC_LDS, CFSEC_CRC_LDS12, CFSEC_SV_CRC):
 //   kBitSliced  gf_bs_crc.hip: coef equals a code mode's network, the inputs checksummed too
 //               (slot[0] >= 0), at most 64^3 tiles of 2 KiB per row and 2^32 - 1 over the stripes
 //   kLookup     gf_crc_lds_kernel: k in {6, 8, 12, 16}, m <= 4; any 6 x 12 matrix with the inputs
 //               checksummed
 //   kVperm      the v_perm kernels: k in {6, 8, 12, 16, 18}, m <= 6; 6 x 12 of EC6P10L2's form (10
-//               rows of 2x2 dyadic blocks + 2 plain rows) with the inputs checksummed
+//               rows of 2x2 dyadic blocks + 2 plain rows) with the inputs checksummed.
+//               kStoreVerify jobs (Reconstruct + Verify, gf_crc_sv_kernel: compared rows checksummed
+//               from the bytes in memory) have this route alone: the same k, 2 <= m <= 6,
+//               0 < nstore < m, every row checksummed (slot[0] >= 0), one length (lens == NULL),
+//               flags set; CFSEC_SV_CRC=0 switches it off
 //   kNone       no fused kernel (every other input count -- 3, 4, 10, 15 -- without its network's
-//               conditions, m > 6, a mode other than kStore, slots outside [0, crc_stride),
-//               crc_stride > 256, len > 2^32 - 1 - 4096): the product and the separate pass
+//               conditions, m > 6, kAccum / kVerify, a kStoreVerify job outside the conditions above,
+//               slots outside [0, crc_stride), crc_stride > 256, len > 2^32 - 1 - 4096): the product
+//               and the separate pass
 enum class CrcRoute : int { kNone = 0, kBitSliced = 1, kLookup = 2, kVperm = 3 };
 CrcRoute matvec_crc_route(const MatVecJob& job, int crc_stride, const int* slot);
 const char* crc_route_name(CrcRoute r);  // "none", "bit-sliced", "lookup", "v_perm"
 // route != kNone.  launch_matvec_crc takes exactly the jobs this accepts, by construction: it
 // dispatches on the same matvec_crc_route answer; callers send everything else to the product and
 // the separate pass (launch_matvec + launch_crc32_to).  CFSEC_TRACE_CRC (read per call) prints
-// "cfsec: crc route=<name> k=.. m=.. cin=.. stripes=.. len=.." to stderr per launch_matvec_crc.
+// "cfsec: crc route=<name> k=.. m=.. cin=.. stripes=.. len=.." to stderr per launch_matvec_crc of a
+// kStore job, "cfsec: crc sv k=.. m=.. nstore=.. stripes=.. len=.. tpw=.. groups=.. per=.." per
+// kStoreVerify job.
 bool matvec_crc_accepts(const MatVecJob& job, int crc_stride, const int* slot);
 hipError_t launch_matvec_crc(const MatVecJob& job, uint32_t* crc, int crc_stride, const int* slot,
                              hipStream_t stream, bool zero = true);
@@ -203,7 +210,8 @@ BsCrcPlan plan_bs_crc(const MatVecJob& job, int resident);
 // workgroups of tpw consecutive tiles by grid_y stripes -- `per` stripes per launch (all of an affine
 // job, else 96 / (k + m), at most 65535; grid_y is the first launch's) -- workgroup g's tiles ending
 // at byte end[g] (its constant is x^(8 (len - end[g]))); dy: -1 the lookup kernel, 0 / 2 / 4 the
-// v_perm kernel's plain / 2x2 / 4x4 dyadic product.  CFSEC_CRC_GROUPS overrides the workgroup total.
+// v_perm kernel's plain / 2x2 / 4x4 dyadic product (a kStoreVerify job: always 0, its rows are decode
+// rows).  CFSEC_CRC_GROUPS overrides the workgroup total.
 struct CrcPlan {
   uint32_t tiles;
   int per, dy;

@@ -139,6 +139,42 @@ class Encoder:
             return out, [[int(words[b * n + i]) for i in range(n)] for b in range(len(bids))]
         return out
 
+    def RepairBatch(self, bids, badIdx, expect=None):
+        """blobnode's repair of a tasklet with the checksum work around it (cfsec_ec_repair_batch_crc):
+        per bid Reconstruct(shards, bad) then Verify(shards), and crc32.ChecksumIEEE of every shard of
+        the bid as it stands after the call -- survivors and rebuilt shards -- for bids whose status is
+        0 or ErrVerify (zeros otherwise).  expect: per bid the n checksums the shards came with;
+        mismatch[b] is then the lowest index of a survivor (a shard outside badIdx[b]) whose checksum
+        differs, or -1.  The check runs after Reconstruct: a bid with mismatch[b] >= 0 was rebuilt
+        from a corrupt survivor and is to be discarded.  Returns (status, crcs, mismatch)."""
+        if len(bids) != len(badIdx):
+            raise ValueError("one bad-index list per bid")
+        if expect is not None and len(expect) != len(bids):
+            raise ValueError("one list of expected checksums per bid")
+        n = len(bids[0]) if bids else 0
+        bm = BatchMarshal(bids, n, fill=True)
+        flat = [i for b in badIdx for i in b]
+        off = [0]
+        for b in badIdx:
+            off.append(off[-1] + len(b))
+        bad = (ctypes.c_int * max(len(flat), 1))(*flat)
+        offs = (ctypes.c_int * len(off))(*off)
+        status = (ctypes.c_int * max(len(bids), 1))()
+        words = (ctypes.c_uint32 * max(len(bids) * n, 1))()
+        mism = (ctypes.c_int * max(len(bids), 1))(*([-1] * max(len(bids), 1)))
+        exp = None
+        if expect is not None:
+            if any(len(e) != n for e in expect):
+                raise ValueError("n expected checksums per bid")
+            exp = (ctypes.c_uint32 * max(len(bids) * n, 1))(*[int(w) & 0xFFFFFFFF for e in expect for w in e])
+        st = self._L.cfsec_ec_repair_batch_crc(self._h, bm.arr, n, len(bids), bad, offs, bm.mem, status, words, exp,
+                                               mism)
+        bm.writeback()
+        _lib.check(st)
+        nb = len(bids)
+        return ([int(status[i]) for i in range(nb)], [[int(words[b * n + i]) for i in range(n)] for b in range(nb)],
+                [int(mism[b]) for b in range(nb)])
+
     def ReconstructBatchAsync(self, bids, badIdx, flags=None, verify: bool = True, stream=None, crcs=None):
         """cfsec_ec_reconstruct_batch_async: bids of device tensors; enqueues on `stream` (default:
         torch's current stream) and returns the per-bid planning status right away.  flags: a zeroed

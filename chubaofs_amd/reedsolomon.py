@@ -173,6 +173,17 @@ class ReedSolomon:
                                                           len(erased), int(data_only), crcs_ptr,
                                                           stream_ptr(stream, device=self.device)))
 
+    def repair_crc_batch(self, ptrs, shard_len: int, nstripes: int, erased, flags_ptr: int, crcs_ptr: int,
+                         stream=None) -> None:
+        """reconstruct_batch of every erased shard, the Verify of the same pass (flags_ptr as
+        verify_batch) and crc32.ChecksumIEEE of every shard as it stands afterwards, survivors
+        included ([stripe][shard], every word filled): blobnode's repair with its checksum work
+        (work_shard_recover.go:654-685, 751-760, 335-342)."""
+        er = (ctypes.c_int * max(len(erased), 1))(*erased)
+        _lib.check(self._L.cfsec_rs_repair_crc_batch(self._h, ptr_array(ptrs), shard_len, nstripes, er,
+                                                     len(erased), flags_ptr, crcs_ptr,
+                                                     stream_ptr(stream, device=self.device)))
+
 
 def _current_device() -> int:
     """The HIP device a handle created with device=-1 binds to (the calling thread's current one)."""

@@ -8,6 +8,7 @@ import "C"
 
 import (
 	"errors"
+	"fmt"
 	"io"
 	"runtime"
 	"unsafe"
@@ -274,6 +275,87 @@ func (e *ECEncoder) reconstructBatch(bids [][][]byte, badIdx [][]int, verify, wa
 		}
 	}
 	return errs, crcs, toError(st)
+}
+
+// ErrCrcNotMatch reports a survivor whose checksum is not the one it came with: blobnode's
+// errCrcNotMatch (work_shard_recover.go:654-685, crc1 != crc2).  Use errors.As to learn the shard.
+type ErrCrcNotMatch struct {
+	Shard int // the lowest index of a survivor whose checksum differs
+}
+
+func (e *ErrCrcNotMatch) Error() string {
+	return fmt.Sprintf("cfsec: shard %d: crc32 does not match the one it was downloaded with", e.Shard)
+}
+
+// RepairBatch is blobnode's repair of a tasklet with the checksum work around it, in one call: per bid
+// the download check of every survivor (work_shard_recover.go:654-685), Reconstruct then Verify
+// (:751-760) and the checksum of each rebuilt shard (:335-342).  crcs[b][i] is crc32.ChecksumIEEE of
+// shard i of bid b as it stands after the call -- survivors and rebuilt shards, global and local --
+// for bids whose errs[b] is nil or ErrVerify (zeros otherwise).  expect (may be nil): per bid the n
+// checksums the shards came with; check[b] is then nil or an *ErrCrcNotMatch naming the lowest
+// survivor (a shard outside badIdx[b]) whose checksum differs.  The check runs after Reconstruct, not
+// before it: a bid with check[b] != nil has been rebuilt from a corrupt survivor and is to be
+// discarded, exactly as one whose download check failed.
+func (e *ECEncoder) RepairBatch(bids [][][]byte, badIdx [][]int, expect [][]uint32) (errs []error, crcs [][]uint32,
+	check []error, err error) {
+	if len(bids) != len(badIdx) || (expect != nil && len(expect) != len(bids)) {
+		return nil, nil, nil, errInvalidArg
+	}
+	errs = make([]error, len(bids))
+	check = make([]error, len(bids))
+	if len(bids) == 0 {
+		return errs, nil, check, nil
+	}
+	n := len(bids[0])
+	flat := make([][]byte, 0, n*len(bids))
+	var bad []C.int
+	off := make([]C.int, 1, len(bids)+1)
+	for b, shards := range bids {
+		if len(shards) != n || (expect != nil && len(expect[b]) != n) {
+			return nil, nil, nil, errInvalidArg
+		}
+		for _, i := range badIdx[b] {
+			if i >= 0 && i < n && len(shards[i]) != 0 {
+				shards[i] = shards[i][:0]
+			}
+			bad = append(bad, C.int(i))
+		}
+		reserve(shards)
+		flat = append(flat, shards...)
+		off = append(off, C.int(len(bad)))
+	}
+	bp := intPtr(bad)
+	status := make([]C.int, len(bids))
+	mismatch := make([]C.int, len(bids))
+	words := make([]C.uint32_t, len(bids)*n)
+	var want []C.uint32_t
+	var wp *C.uint32_t
+	if expect != nil {
+		want = make([]C.uint32_t, len(bids)*n)
+		for b := range expect {
+			for i, w := range expect[b] {
+				want[b*n+i] = C.uint32_t(w)
+			}
+		}
+		wp = &want[0]
+	}
+	st := callVec(flat, func(v *C.cfsec_shard, _ C.int) C.int {
+		return C.cfsec_ec_repair_batch_crc(e.h, v, C.int(n), C.int(len(bids)), bp, &off[0], C.CFSEC_MEM_HOST,
+			&status[0], &words[0], wp, &mismatch[0])
+	})
+	crcs = make([][]uint32, len(bids))
+	for b := range bids {
+		copy(bids[b], flat[b*n:(b+1)*n])
+		errs[b] = ecError(status[b])
+		crcs[b] = make([]uint32, n)
+		for i := range crcs[b] {
+			crcs[b][i] = uint32(words[b*n+i])
+		}
+		if expect != nil && mismatch[b] >= 0 {
+			check[b] = &ErrCrcNotMatch{Shard: int(mismatch[b])}
+		}
+	}
+	return errs, crcs, check, toError(st)
 }
 
 // EncodeBatch is access's Put over a batch of blobs (stream_put.go:104-143 encodes them one by one):

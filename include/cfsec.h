@@ -87,7 +87,7 @@ typedef struct cfsec_ec cfsec_ec;
 /* ---------------- library ---------------- */
 /* "cfsec MAJOR.MINOR.PATCH (gfx950)".  ABI history: 0.2.0 inserted src_len into
  * cfsec_crc32block_decode / cfsec_crc32block_decode_batch (callers built against 0.1.0 must be
- * rebuilt); 0.3.0 and 0.4.0 add entry points only. */
+ * rebuilt); 0.3.0, 0.4.0 and 0.5.0 add entry points only. */
 const char* cfsec_version(void);
 /* Message for the last CFSEC_ERR_DEVICE on this thread ("" if none). */
 const char* cfsec_last_error(void);
@@ -158,6 +158,15 @@ int cfsec_rs_encode_crc_batch(cfsec_rs* h, uint8_t* const* ptrs, size_t shard_si
 int cfsec_rs_reconstruct_crc_batch(cfsec_rs* h, uint8_t* const* ptrs, size_t shard_size, int nstripes,
                                    const int* erased, int nerased, int data_only, uint32_t* crcs,
                                    void* stream);
+/* blobnode's repair with the checksum work around it: cfsec_rs_reconstruct_crc_batch (every erased
+ * shard rebuilt) with the Verify of the same pass (flags as cfsec_rs_verify_batch: flags[s] is OR-ed
+ * with 1 when a surviving parity shard outside the first data_shards survivors does not match;
+ * caller zeroes it) and every word of crcs filled: crcs[s * (data+parity) + i] = crc32.ChecksumIEEE
+ * of shard i as it stands in memory after the call, survivors and rebuilt shards.  One fused pass
+ * for k in {6,8,12,16,18} and 2..6 rebuilt + compared shards; other shapes take the product plus the
+ * separate checksum pass, same words.  CFSEC_ERR_NOT_SUPPORTED for more than 32 data shards. */
+int cfsec_rs_repair_crc_batch(cfsec_rs* h, uint8_t* const* ptrs, size_t shard_size, int nstripes,
+                              const int* erased, int nerased, uint32_t* flags, uint32_t* crcs, void* stream);
 
 /* ---------------- stripe batches over one or more GPUs ----------------
  * The reference codes one stripe per call: access encodes blob by blob (access/stream_put.go:104-143,
@@ -238,6 +247,23 @@ int cfsec_ec_encode_batch_crc(cfsec_ec* h, cfsec_shard* shards, int n, int nstri
                               uint32_t* crcs);
 int cfsec_ec_reconstruct_batch_crc(cfsec_ec* h, cfsec_shard* shards, int n, int nbids, const int* bad_idx,
                                    const int* bad_off, int verify, int mem, int* status, uint32_t* crcs);
+/* blobnode's repair of a tasklet with the checksum work around it (work_shard_recover.go:654-685,
+ * 751-760, 335-342): per bid Reconstruct then Verify as cfsec_ec_reconstruct_batch(verify = 1), and
+ * crcs[b*n + i] = crc32.ChecksumIEEE of shard i as it stands in the caller's memory after the call --
+ * survivors and rebuilt shards, global and local -- for every bid whose status is CFSEC_OK or
+ * CFSEC_ERR_VERIFY; all-zero words for a bid with any other status.  expect (host, nbids*n words, may
+ * be NULL): the checksum each survivor came with; mismatch[b] (may be NULL when expect is) = the
+ * lowest index of a survivor (a shard outside bad_b) whose word differs, or -1.  status[] keeps the
+ * meaning it has in cfsec_ec_reconstruct_batch.  CFSEC_ERR_NOT_SUPPORTED as for the _crc form.
+ * The survivors are read once: the pass that rebuilds and compares also checksums them, where a fused
+ * kernel covers the shape (RS decode jobs of k in {6,8,12,16,18} with 2..6 rebuilt + compared rows,
+ * device or page-locked memory, one shard size per bad set); elsewhere a separate checksum pass
+ * gives the same words.  So the survivors' check runs after Reconstruct, not before it: a bid with
+ * mismatch[b] >= 0 has been rebuilt from a corrupt survivor and must be discarded, as one that
+ * failed its download check. */
+int cfsec_ec_repair_batch_crc(cfsec_ec* h, cfsec_shard* shards, int n, int nbids, const int* bad_idx,
+                              const int* bad_off, int mem, int* status, uint32_t* crcs, const uint32_t* expect,
+                              int* mismatch);
 /* Asynchronous forms of the two batch calls above, for device memory on the handle's (first) device:
  * the call plans the batch, enqueues its kernels on `stream` (hipStream_t; NULL = the legacy default
  * stream) and returns without waiting, so a caller overlaps the next tasklet's planning with this
