@@ -22,6 +22,7 @@
 // with shift(~0, size) ^ ~0 folded in by the last block, so the accumulated word is ChecksumIEEE.
 // Every payload byte is read once and written once.
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 
 #include "gf_crc.hpp"
@@ -427,6 +428,14 @@ hipError_t launch(const Crc32BlockJob& j, hipStream_t stream) {
     if (SEAMLESS_PROBE) a.out_stride = j.block_len;
   }
   if (nb <= 0 || j.n == 0) return hipSuccess;
+  // CFSEC_TRACE_BLK (read per call: tests turn it on mid-process): one stderr line per kernel launch
+  const char* const tv = std::getenv("CFSEC_TRACE_BLK");
+  const bool trace = tv && tv[0] && tv[0] != '0';
+  const auto traced = [&](int ny, unsigned g, unsigned resident) {
+    if (trace)
+      std::fprintf(stderr, "cfsec: blk launch encode=%u objects=%d blocks=%u items=%u grid=%u resident=%u\n", a.encode, ny,
+                   a.nb, a.items, g, resident);
+  };
   if (nb > 0xFFFFFFFFll / kSlots || j.n < 0 || !j.in || (!j.out && (j.encode || j.to > j.from)) || (!j.encode && !j.bad))
     return hipErrorInvalidValue;
   a.bad = j.bad;
@@ -488,11 +497,15 @@ hipError_t launch(const Crc32BlockJob& j, hipStream_t stream) {
       }();
       const unsigned per = cap ? (a.items + cap - 1) / cap : 1;
       const unsigned g = full && cap ? std::min(cap, a.items) : (a.items + per - 1) / per;
+      traced(ny, g, cap);
       hipLaunchKernelGGL((crc32block_block_kernel<RING, NTS, true>), dim3(g), dim3(256), 0, stream, a);
-    } else if (FASTEPI && ONE && EPI && STORE && CRC)
+    } else if (FASTEPI && ONE && EPI && STORE && CRC) {
+      traced(ny, a.items, 0);
       hipLaunchKernelGGL((crc32block_block_kernel<RING, NTS, false>), dim3(a.items), dim3(256), 0, stream, a);
-    else
+    } else {
+      traced(ny, grid, 0);
       hipLaunchKernelGGL((crc32block_kernel<STORE, CRC, EPI, SRCALIGN, NTS>), dim3(grid), dim3(256), 0, stream, a);
+    }
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     if (a.bad) a.bad += ny;

@@ -225,7 +225,12 @@ uint32_t crc32_shift_ones(size_t len);
 
 // blobstore/common/crc32block framing (crc32block.hip): blocks of block_len bytes, each the
 // little-endian crc32.ChecksumIEEE of its payload (block_len - 4 bytes, less in the last block)
-// followed by the payload.  Device pointers.
+// followed by the payload.  Device pointers.  CFSEC_TRACE_BLK (read per call) prints one stderr line
+// per kernel launch -- at most 128 objects each --
+//   cfsec: blk launch encode=<0|1> objects=<n> blocks=<per object> items=<blocks x objects> grid=<workgroups>
+//   resident=<workgroups of the strided kernel the device holds at once>
+// (one line; grid = min(resident, items), or under CFSEC_BLK_GRID=0, read once per process, the fewest
+// workgroups that give every one ceil(items / resident) blocks).
 struct Crc32BlockJob {
   bool encode = true;
   int n = 1;                           // objects, all of the same payload size
