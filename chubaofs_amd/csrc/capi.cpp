@@ -586,6 +586,10 @@ int cfsec_host_free(void* p) {
 int cfsec_crc32_ieee_batch(uint8_t* const* ptrs, size_t shard_size, int n, uint32_t* out,
                            int device, void* stream) {
   if ((!ptrs && n > 0) || !out || n < 0) return CFSEC_ERR_INVALID_ARG;
+  if (n > 0 && shard_size > 0xFFFFFFFFull - 4096) {  // launch_crc32_to's limit: boundary misuse, no device failure
+    cfsec::set_last_error("cfsec_crc32_ieee_batch: shard_size above 2^32 - 1 - 4096");
+    return CFSEC_ERR_INVALID_ARG;
+  }
   return guarded([&] {
     if (device < 0 && hipGetDevice(&device) != hipSuccess) return (int)CFSEC_ERR_DEVICE;
     cfsec::DeviceContext* ctx = cfsec::DeviceContext::get(device);

@@ -12,6 +12,7 @@
 // atomicXor into the shard's word.  `fin` (crc32_shift_ones(S), or 0 for the raw word) is folded in
 // by workgroup 0.
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 #include <vector>
 
@@ -26,8 +27,9 @@ using crcdev::kTile;
 using dev::u32x4;
 // Argument block: the fixed fields, then a flexible area of words holding the group constants
 // gconst[0 .. ng) (x^(8(len - e_g)) mod P, the same for every shard) followed by the shard pointers
-// and their output words: a launch carries as many shards as fit beside its ng constants (256 shards
-// at ng = 16: a repair tasklet's rebuilt rows in one launch).
+// and their output words: a launch carries as many shards as fit beside its ng constants, 3 words
+// each (plan_crc32's slots: 266 at ng <= 2, 261 at ng = 16 -- a repair tasklet's 256 rebuilt rows in
+// one launch --, 138 at ng = 384); an equally spaced list needs one pointer and one word.
 constexpr int kFlexWords = 800;
 
 struct __attribute__((aligned(16))) CrcArgs {
@@ -131,6 +133,28 @@ uint32_t probe_groups() {
 
 }  // namespace
 
+// ~`total` (4096) workgroups in all, but each folding >= 16 tiles: its fixed cost (the 32-word
+// alignment basis of every thread, 32 KiB from L2, and the step table) must not outweigh its tiles.
+// Round 3, event-timed (tools/crc_pass_probe.hip, profiles/r03/crc_pass.txt): a tasklet's 256 rebuilt
+// rows of 64 tiles 21 us at 4 workgroups per row vs 34 us at 16; 128 rows of 1366 tiles 126 us at 32
+// per row (5.67 TB/s) vs 132-134 at 8-16.  Then as many shards per launch as fit beside the group
+// constants.
+Crc32Plan plan_crc32(size_t len, int n, bool affine, uint32_t total) {
+  Crc32Plan p;
+  p.tiles = (uint32_t)((len + kTile - 1) / kTile);
+  const uint32_t want = std::max<uint32_t>(1, std::min<uint32_t>(total / (uint32_t)n, p.tiles / 16));
+  p.groups = std::min<uint32_t>({p.tiles, want, (uint32_t)kMaxGroups});
+  p.tpw = (p.tiles + p.groups - 1) / p.groups;
+  p.groups = (p.tiles + p.tpw - 1) / p.tpw;
+  p.pw = (p.groups + 1) & ~1u;                        // pointers 8-byte aligned
+  p.slots = (int)((kFlexWords - p.pw) / 3);           // 2 words of pointer + 1 of index
+  p.per_launch = affine ? n : std::min(n, p.slots);
+  p.end.resize(p.groups);
+  for (uint32_t g = 0; g < p.groups; ++g)
+    p.end[g] = (int64_t)std::min<uint64_t>((uint64_t)(g + 1) * p.tpw, p.tiles) * kTile;
+  return p;
+}
+
 hipError_t launch_crc32_to(const uint8_t* const* ptrs, size_t len, int n, uint32_t* out, const uint32_t* idx,
                            uint32_t fin, hipStream_t stream) {
   if (len == 0 || n == 0) return hipSuccess;
@@ -138,40 +162,28 @@ hipError_t launch_crc32_to(const uint8_t* const* ptrs, size_t len, int n, uint32
   CrcArgs a{};
   hipError_t e = crc_device_tables(&a.tabs);
   if (e != hipSuccess) return e;
-  const uint32_t tiles = (uint32_t)((len + kTile - 1) / kTile);
   // one launch for an equally spaced list (a pitched stripe batch) with consecutive words
   const auto at = [&](int i) { return (int64_t)(uintptr_t)ptrs[i]; };
   int64_t stride = n > 1 ? at(1) - at(0) : 0;
   for (int i = 1; i < n && stride; ++i)
     if (at(i) - at(0) != stride * i || (idx && idx[i] != idx[0] + (uint32_t)i)) stride = 0;
   if (n > 65535) stride = 0;
-  // ~4096 workgroups in all, but each folding >= 16 tiles: its fixed cost (the 32-word alignment
-  // basis of every thread, 32 KiB from L2, and the step table) must not outweigh its tiles.  Round 3,
-  // event-timed (tools/crc_pass_probe.hip, profiles/r03/crc_pass.txt): a tasklet's 256 rebuilt rows
-  // of 64 tiles 21 us at 4 workgroups per row vs 34 us at 16; 128 rows of 1366 tiles 126 us at 32
-  // per row (5.67 TB/s) vs 132-134 at 8-16.  Then as many shards per launch as fit beside the group
-  // constants.
-  const uint32_t total = probe_groups() ? probe_groups() : 4096u;
-  const uint32_t want = std::max<uint32_t>(1, std::min<uint32_t>(total / (uint32_t)n, tiles / 16));
-  uint32_t groups = std::min<uint32_t>({tiles, want, (uint32_t)kMaxGroups});
-  const uint32_t tpw = (tiles + groups - 1) / groups;
-  groups = (tiles + tpw - 1) / tpw;
-  const uint32_t pw = (groups + 1) & ~1u;                       // pointers 8-byte aligned
-  const int slots = (int)((kFlexWords - pw) / 3);              // 2 words of pointer + 1 of index
-  const int per_launch = stride ? n : std::min(n, slots);
+  const Crc32Plan p = plan_crc32(len, n, stride != 0, probe_groups() ? probe_groups() : 4096u);
+  const uint32_t groups = p.groups;
+  const int per_launch = p.per_launch;
+  // CFSEC_TRACE_CRC32 (read per call: tests turn it on mid-process): one stderr line per kernel launch
+  const char* const tv = std::getenv("CFSEC_TRACE_CRC32");
+  const bool trace = tv && tv[0] && tv[0] != '0';
   a.len = len;
   a.sstride = stride;
-  a.tiles = tiles;
-  a.tpw = tpw;
+  a.tiles = p.tiles;
+  a.tpw = p.tpw;
   a.out = out;
   a.fin = fin;
   a.ng = groups;
-  a.pw = pw;
-  a.iw = pw + 2 * (uint32_t)(stride ? 1 : per_launch);
-  for (uint32_t g = 0; g < groups; ++g) {
-    const int64_t end = (int64_t)std::min<uint64_t>((uint64_t)(g + 1) * tpw, tiles) * kTile;
-    a.flex[g] = crc_xpow(8 * ((int64_t)len - end));
-  }
+  a.pw = p.pw;
+  a.iw = p.pw + 2 * (uint32_t)(stride ? 1 : per_launch);
+  for (uint32_t g = 0; g < groups; ++g) a.flex[g] = crc_xpow(8 * ((int64_t)len - p.end[g]));
   for (int s0 = 0; s0 < n; s0 += per_launch) {
     const int ns = std::min(per_launch, n - s0);
     const uint8_t** pp = reinterpret_cast<const uint8_t**>(a.flex + a.pw);
@@ -180,6 +192,9 @@ hipError_t launch_crc32_to(const uint8_t* const* ptrs, size_t len, int n, uint32
       pp[s] = ptrs[s0 + s];
       ip[s] = idx ? idx[s0 + s] : (uint32_t)(s0 + s);
     }
+    if (trace)
+      std::fprintf(stderr, "cfsec: crc32 len=%llu shards=%d s0=%d tiles=%u groups=%u tpw=%u affine=%d idx=%d fin=%d\n",
+                   (unsigned long long)len, ns, s0, p.tiles, groups, p.tpw, stride != 0, idx != nullptr, fin != 0);
     hipLaunchKernelGGL(crc32_horner_kernel, dim3(groups, (unsigned)ns), dim3(256), 0, stream, a);
     e = hipGetLastError();
     if (e != hipSuccess) return e;

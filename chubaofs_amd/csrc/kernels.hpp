@@ -141,6 +141,25 @@ uint32_t crc32_finalize(uint32_t raw, size_t len);
 // (crc32_shift_ones(len) gives crc32.ChecksumIEEE directly).
 hipError_t launch_crc32_to(const uint8_t* const* ptrs, size_t len, int n, uint32_t* out, const uint32_t* idx,
                            uint32_t fin, hipStream_t stream);
+// The launches of that pass, decided the way plan_matvec_crc decides the fused kernels': a pure host
+// function (no HIP calls) of the shard length (0 < len <= 2^32 - 1 - 4096), the list's shard count
+// n > 0, whether the list is affine -- equally spaced pointers with consecutive words and at most
+// 65535 shards, which launch_crc32_to finds out -- and `total`, the workgroups aimed at over the whole
+// list (4096, or CFSEC_CRC32_GROUPS_PROBE, read per call).  A shard is `tiles` tiles of 4 KiB; every
+// launch is `groups` workgroups of tpw consecutive tiles (at least 16 where the shard has them, at
+// most 384 groups) by per_launch shards, workgroup g's tiles ending at byte end[g] (its constant is
+// x^(8 (len - end[g]))).  The argument block's 800 flexible words hold the constants, padded to `pw`
+// words, then the pointers and words of the shards: `slots` = (800 - pw) / 3 shards of a pointer-table
+// launch, per_launch = min(n, slots); an affine list needs one pointer, per_launch = n.
+// CFSEC_TRACE_CRC32 (read per call) prints one stderr line per kernel launch:
+// "cfsec: crc32 len=.. shards=<of this launch> s0=<its first shard> tiles=.. groups=.. tpw=..
+// affine=<0|1> idx=<0|1: scattered words> fin=<0|1: fin != 0>".
+struct Crc32Plan {
+  uint32_t tiles, groups, tpw, pw;
+  int slots, per_launch;
+  std::vector<int64_t> end;
+};
+Crc32Plan plan_crc32(size_t len, int n, bool affine, uint32_t total);
 
 // Encode / reconstruct (kStore) and Reconstruct + Verify (kStoreVerify) with crc32.ChecksumIEEE of the rows the product touches, fused
 // into the product kernel (gf_crc.hpp): row i of the product (inputs 0..k-1, then outputs) has its

@@ -344,7 +344,8 @@ int cfsec_host_alloc(size_t size, void** out);
 int cfsec_host_free(void* p);
 
 /* ---------------- shard CRC32 (access/stream_put.go:249-253) ---------------- */
-/* crc32.ChecksumIEEE of each device shard; out: host array of n uint32. Synchronous. */
+/* crc32.ChecksumIEEE of each device shard; out: host array of n uint32. Synchronous.
+ * shard_size above 2^32 - 1 - 4096 is CFSEC_ERR_INVALID_ARG: nothing is launched or read. */
 int cfsec_crc32_ieee_batch(uint8_t* const* ptrs, size_t shard_size, int n, uint32_t* out,
                            int device, void* stream);
 

@@ -143,7 +143,8 @@ def test_crc_zero_length_and_empty(rs):
 @pytest.mark.parametrize("n,S", [(170, 4097), (2048, 300), (7, 349526)])
 def test_standalone_crc_many_shards(rs, layout, n, S):
     """cfsec_crc32_ieee_batch over many shards: an equally spaced list runs as one launch, a
-    scattered list in pointer-table launches of 160."""
+    scattered list in pointer-table launches of as many shards as fit beside the group constants (266 at
+    one group, 264 at the five of S = 349526: plan_crc32)."""
     r = np.random.default_rng(n + S)
     if layout == "pitched":
         pitch = (S + 255) // 256 * 256
