@@ -154,7 +154,9 @@ def test_reconstruct_stripes_16_20_dyadic_repair(memory, verify):
 
 @pytest.mark.parametrize("memory", ["host", "device"])
 def test_reconstruct_stripes_many_patterns_and_launch_splits(memory):
-    """70 stripes (more than one launch's 32 length slots), 9 erasure patterns, varied sizes."""
+    """70 stripes of varied sizes over 9 erasure patterns.  The batch layer groups stripes by plan, so
+    every launch group here holds 7 or 8 stripes against capacities of 18 to 22: no group is split over
+    two launches (tests/test_gpu_varlen_edges.py runs the split)."""
     from chubaofs_amd import reedsolomon
     k, m = 12, 4
     enc = reedsolomon.New(k, m, device=0)
