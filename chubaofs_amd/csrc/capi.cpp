@@ -41,6 +41,22 @@ int guarded(F&& f) {
   }
 }
 
+// A bid batch's bad-shard lists: bad_idx[bad_off[b] .. bad_off[b + 1]), offsets from 0 and ascending.
+// mismatch (when given): -1 for every bid whose offsets passed.
+bool bad_off_valid(int nbids, const int* bad_off, const int* bad_idx, int* mismatch = nullptr) {
+  if (nbids > 0 && bad_off[0] != 0) return false;
+  for (int b = 0; b < nbids; ++b) {
+    if (bad_off[b + 1] < bad_off[b] || (bad_off[b + 1] > bad_off[b] && !bad_idx)) return false;
+    if (mismatch) mismatch[b] = -1;
+  }
+  return true;
+}
+
+// The checksum words of a batch call of `items` items of n shards each.
+cfsec::CrcOut crc_out(uint32_t* words, int items, int n, bool every = false) {
+  return cfsec::CrcOut{words, (size_t)items * n, every};
+}
+
 // codemode.go:56-79 (the constCodeModeTactic table), keyed by the CodeMode values of
 // codemode.go:26-44.
 struct ModeRow {
@@ -72,6 +88,41 @@ int64_t crc32block_framed(int64_t size, int64_t block_len) {
   return size + 4 * ((size + p - 1) / p);
 }
 
+// The blocks [b0, b0 + nb) a decode of the payload range [from, to) touches and f1, the framed end
+// of the last of them (the whole object for an encode).  from == to touches the block `from` lies
+// inside, and none when it sits on a block boundary (see crc32block.hip).
+struct BlockRange {
+  int64_t b0, nb, f1;
+};
+BlockRange blocks_touched(bool encode, int64_t size, int64_t block_len, int64_t from, int64_t to) {
+  const int64_t P = block_len - 4;
+  BlockRange r{0, (size + P - 1) / P, 0};
+  if (!encode) {
+    r.b0 = from / P;
+    const int64_t b1 = from < to ? (to - 1) / P : (from % P ? r.b0 : r.b0 - 1);
+    r.nb = b1 - r.b0 + 1;
+  }
+  r.f1 = std::min(crc32block_framed(size, block_len), (r.b0 + r.nb) * block_len);
+  return r;
+}
+
+// Decoder.Reader reads the touched blocks through an io.SectionReader: a framed object that ends
+// before them is io.ErrUnexpectedEOF there (decode.go:94-97, 126-130), ErrShortData here --
+// checked before any copy or launch, so nothing reads past the caller's buffer.
+bool decode_source_short(const BlockRange& r, int64_t src_len) {
+  if (r.nb <= 0 || src_len >= r.f1) return false;
+  cfsec::set_last_error("crc32block decode: framed source shorter than the blocks the range touches");
+  return true;
+}
+
+// The context of `device` (< 0: the current one), or nullptr.
+cfsec::DeviceContext* device_context(int device) {
+  if (device < 0 && hipGetDevice(&device) != hipSuccess) return nullptr;
+  cfsec::DeviceContext* ctx = cfsec::DeviceContext::get(device);
+  if (!ctx) cfsec::set_last_error("no HIP device available to the cfsec engine");
+  return ctx;
+}
+
 // Encoder.Encode / Decoder.Reader through launch_crc32block: device pointers in place, page-locked
 // host buffers in place (device aliases), other host memory staged through the workspace.
 int crc32block_call(bool encode, const uint8_t* src, int64_t src_len, int64_t size, int64_t block_len, int64_t from,
@@ -82,62 +133,40 @@ int crc32block_call(bool encode, const uint8_t* src, int64_t src_len, int64_t si
   if (!encode && (from < 0 || from > to || to > size)) return CFSEC_ERR_INVALID_ARG;
   if (bad_block) *bad_block = -1;
   if (shard_crc) *shard_crc = 0;  // crc32.ChecksumIEEE(nil)
-  const int64_t P = block_len - 4;
-  int64_t b0 = 0, nb = (size + P - 1) / P;  // blocks the call touches
-  if (!encode) {
-    b0 = from / P;
-    const int64_t b1 = from < to ? (to - 1) / P : (from % P ? b0 : b0 - 1);  // see crc32block.hip
-    nb = b1 - b0 + 1;
-  }
-  if (nb <= 0) return CFSEC_OK;
-  const int64_t framed = crc32block_framed(size, block_len);
-  const int64_t f0 = b0 * block_len, f1 = std::min(framed, (b0 + nb) * block_len);
-  const int64_t in_bytes = encode ? size : f1 - f0;
-  const int64_t out_bytes = encode ? framed : to - from;
+  const BlockRange r = blocks_touched(encode, size, block_len, from, to);
+  if (r.nb <= 0) return CFSEC_OK;
+  const int64_t f0 = r.b0 * block_len;
+  const int64_t in_bytes = encode ? size : r.f1 - f0;
+  const int64_t out_bytes = encode ? r.f1 : to - from;
   if (!src || (!dst && out_bytes > 0)) return CFSEC_ERR_INVALID_ARG;
-  // Decoder.Reader reads the touched blocks through an io.SectionReader: a framed object that ends
-  // before them is io.ErrUnexpectedEOF there (decode.go:94-97, 126-130), ErrShortData here --
-  // checked before any copy or launch, so nothing reads past the caller's buffer.
-  if (!encode && src_len < f1) {
-    cfsec::set_last_error("crc32block decode: framed source shorter than the blocks the range touches");
-    return CFSEC_ERR_SHORT_DATA;
-  }
+  if (!encode && decode_source_short(r, src_len)) return CFSEC_ERR_SHORT_DATA;
   return guarded([&] {
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) return (int)CFSEC_ERR_DEVICE;
-    cfsec::DeviceContext* ctx = cfsec::DeviceContext::get(device);
-    if (!ctx) {
-      cfsec::set_last_error("no HIP device available to the cfsec engine");
-      return (int)CFSEC_ERR_DEVICE;
-    }
-    cfsec::DeviceGuard g(device);
-    if (!g.ok()) return cfsec::hip_status(hipErrorInvalidDevice, "hipSetDevice");
-    const uint8_t* din = src;
-    uint8_t* dout = dst;
+    cfsec::DeviceContext* ctx = device_context(device);
+    if (!ctx) return (int)CFSEC_ERR_DEVICE;
+    // the launch addresses the framed object from its start; what is aliased or staged begins at block b0
+    const uint8_t* first = src + (encode ? 0 : f0);
+    uint8_t *pi = nullptr, *po = dst;
     bool stage = false;
     if (mem == CFSEC_MEM_HOST) {
-      uint8_t *pi = nullptr, *po = nullptr;
-      const bool pin_in = cfsec::device_alias(const_cast<uint8_t*>(src) + (encode ? 0 : f0), &pi);
-      const bool pin_out = out_bytes == 0 || cfsec::device_alias(dst, &po);
-      stage = !(pin_in && pin_out);
-      if (!stage) {
-        din = encode ? pi : reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(pi) - (uintptr_t)f0);
-        dout = po;
-      }
+      cfsec::DeviceGuard g(ctx->device());
+      if (!g.ok()) return cfsec::hip_status(hipErrorInvalidDevice, "hipSetDevice");
+      stage = !cfsec::device_alias(const_cast<uint8_t*>(first), &pi) ||
+              (out_bytes > 0 && !cfsec::device_alias(dst, &po));
     }
-    cfsec::DeviceContext::Workspace* ws = nullptr;
-    int st = ctx->acquire(stage ? (size_t)(in_bytes + out_bytes) : 0, 2, &ws);
-    if (st != CFSEC_OK) return st;
-    hipStream_t s = stream ? as_stream(stream) : ws->stream;
-    if (!stream && !stage) st = ctx->order_after_default(ws);
-    if (st == CFSEC_OK && stage) {
-      st = cfsec::hip_status(hipMemcpyAsync(ws->dbuf, src + (encode ? 0 : f0), (size_t)in_bytes, hipMemcpyHostToDevice, s),
-                             "hipMemcpyAsync H2D");
-      // the launch addresses the framed object from its start; the staged copy begins at block b0
-      din = encode ? ws->dbuf : reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(ws->dbuf) - (uintptr_t)f0);
-      dout = ws->dbuf + in_bytes;
+    cfsec::SyncCall call(ctx, stage ? (size_t)(in_bytes + out_bytes) : 0, 2, as_stream(stream), !stream && !stage);
+    if (!call.begun()) return call.status();
+    cfsec::DeviceContext::Workspace* ws = call.ws();
+    hipStream_t s = call.stream();
+    if (stage) {
+      call.copy(ws->dbuf, first, (size_t)in_bytes, hipMemcpyHostToDevice);
+      pi = ws->dbuf;
+      po = ws->dbuf + in_bytes;
     }
-    if (st == CFSEC_OK) st = cfsec::hip_status(hipMemsetAsync(ws->dflags, 0xFF, 4, s), "hipMemsetAsync");
-    if (st == CFSEC_OK) st = cfsec::hip_status(hipMemsetAsync(ws->dflags + 1, 0, 4, s), "hipMemsetAsync");
+    const uintptr_t base = reinterpret_cast<uintptr_t>(mem == CFSEC_MEM_HOST ? pi : first);
+    const uint8_t* din = reinterpret_cast<const uint8_t*>(base - (uintptr_t)(encode ? 0 : f0));
+    uint8_t* dout = po;
+    call.memset(ws->dflags, 0xFF, 4);
+    call.memset(ws->dflags + 1, 0, 4);
     cfsec::Crc32BlockJob j;
     j.encode = encode;
     j.n = 1;
@@ -149,22 +178,17 @@ int crc32block_call(bool encode, const uint8_t* src, int64_t src_len, int64_t si
     j.to = to;
     j.bad = ws->dflags;
     j.whole = (encode && shard_crc) ? ws->dflags + 1 : nullptr;
-    if (st == CFSEC_OK) st = cfsec::hip_status(cfsec::launch_crc32block(j, s), "launch_crc32block");
-    if (st == CFSEC_OK && stage && out_bytes > 0)
-      st = cfsec::hip_status(hipMemcpyAsync(dst, dout, (size_t)out_bytes, hipMemcpyDeviceToHost, s),
-                             "hipMemcpyAsync D2H");
-    if (st == CFSEC_OK)
-      st = cfsec::hip_status(hipMemcpyAsync(ws->hflags, ws->dflags, 8, hipMemcpyDeviceToHost, s), "hipMemcpyAsync D2H");
-    const int sync = ctx->finish(ws, s);
-    if (st == CFSEC_OK) st = sync;
+    call.step("launch_crc32block", [&] { return cfsec::launch_crc32block(j, s); });
+    if (stage && out_bytes > 0) call.copy(dst, dout, (size_t)out_bytes, hipMemcpyDeviceToHost);
+    call.fetch_words(2);
+    int st = call.finish();
     if (st == CFSEC_OK) {
       if (encode && shard_crc) *shard_crc = ws->hflags[1];
       if (!encode && ws->hflags[0] != 0xFFFFFFFFu) {
-        if (bad_block) *bad_block = b0 + (int64_t)ws->hflags[0];
+        if (bad_block) *bad_block = r.b0 + (int64_t)ws->hflags[0];
         st = CFSEC_ERR_MISMATCHED_CRC;
       }
     }
-    ctx->release(ws);
     return st;
   });
 }
@@ -437,9 +461,7 @@ int cfsec_ec_set_devices(cfsec_ec* h, const int* devices, int ndev) {
 int cfsec_ec_reconstruct_batch(cfsec_ec* h, cfsec_shard* shards, int n, int nbids, const int* bad_idx,
                                const int* bad_off, int verify, int mem, int* status) {
   if (!h || nbids < 0 || n <= 0 || (nbids > 0 && (!shards || !status || !bad_off))) return CFSEC_ERR_INVALID_ARG;
-  if (nbids > 0 && bad_off[0] != 0) return CFSEC_ERR_INVALID_ARG;  // offsets index bad_idx from 0
-  for (int b = 0; b < nbids; ++b)
-    if (bad_off[b + 1] < bad_off[b] || (bad_off[b + 1] > bad_off[b] && !bad_idx)) return CFSEC_ERR_INVALID_ARG;
+  if (!bad_off_valid(nbids, bad_off, bad_idx)) return CFSEC_ERR_INVALID_ARG;
   return guarded([&] { return h->e->reconstruct_batch(shards, n, nbids, bad_idx, bad_off, mem, verify != 0, status); });
 }
 
@@ -452,13 +474,9 @@ int cfsec_ec_reconstruct_batch_crc(cfsec_ec* h, cfsec_shard* shards, int n, int 
                                    const int* bad_off, int verify, int mem, int* status, uint32_t* crcs) {
   if (!h || nbids < 0 || n <= 0 || (nbids > 0 && (!shards || !status || !bad_off || !crcs)))
     return CFSEC_ERR_INVALID_ARG;
-  if (nbids > 0 && bad_off[0] != 0) return CFSEC_ERR_INVALID_ARG;
-  for (int b = 0; b < nbids; ++b)
-    if (bad_off[b + 1] < bad_off[b] || (bad_off[b + 1] > bad_off[b] && !bad_idx)) return CFSEC_ERR_INVALID_ARG;
+  if (!bad_off_valid(nbids, bad_off, bad_idx)) return CFSEC_ERR_INVALID_ARG;
   std::memset(crcs, 0, sizeof(uint32_t) * (size_t)nbids * n);
-  cfsec::CrcOut c;
-  c.words = crcs;
-  c.n = (size_t)nbids * n;
+  const cfsec::CrcOut c = crc_out(crcs, nbids, n);
   return guarded([&] {
     return h->e->reconstruct_batch(shards, n, nbids, bad_idx, bad_off, mem, verify != 0, status, nullptr, &c);
   });
@@ -469,16 +487,9 @@ int cfsec_ec_repair_batch_crc(cfsec_ec* h, cfsec_shard* shards, int n, int nbids
                               int* mismatch) {
   if (!h || nbids < 0 || n <= 0 || (nbids > 0 && (!shards || !status || !bad_off || !crcs)) || (expect && !mismatch))
     return CFSEC_ERR_INVALID_ARG;
-  if (nbids > 0 && bad_off[0] != 0) return CFSEC_ERR_INVALID_ARG;
-  for (int b = 0; b < nbids; ++b) {
-    if (bad_off[b + 1] < bad_off[b] || (bad_off[b + 1] > bad_off[b] && !bad_idx)) return CFSEC_ERR_INVALID_ARG;
-    if (mismatch) mismatch[b] = -1;
-  }
+  if (!bad_off_valid(nbids, bad_off, bad_idx, mismatch)) return CFSEC_ERR_INVALID_ARG;
   std::memset(crcs, 0, sizeof(uint32_t) * (size_t)nbids * n);
-  cfsec::CrcOut c;
-  c.words = crcs;
-  c.n = (size_t)nbids * n;
-  c.every = true;
+  const cfsec::CrcOut c = crc_out(crcs, nbids, n, true);
   const int rc = guarded([&] {
     return h->e->reconstruct_batch(shards, n, nbids, bad_idx, bad_off, mem, true, status, nullptr, &c);
   });
@@ -499,9 +510,7 @@ int cfsec_ec_encode_batch_crc(cfsec_ec* h, cfsec_shard* shards, int n, int nstri
                               uint32_t* crcs) {
   if (!h || nstripes < 0 || n <= 0 || (nstripes > 0 && (!shards || !status || !crcs))) return CFSEC_ERR_INVALID_ARG;
   std::memset(crcs, 0, sizeof(uint32_t) * (size_t)nstripes * n);
-  cfsec::CrcOut c;
-  c.words = crcs;
-  c.n = (size_t)nstripes * n;
+  const cfsec::CrcOut c = crc_out(crcs, nstripes, n);
   return guarded([&] { return h->e->encode_batch(shards, n, nstripes, mem, status, nullptr, &c); });
 }
 
@@ -509,16 +518,12 @@ int cfsec_ec_reconstruct_batch_async(cfsec_ec* h, cfsec_shard* shards, int n, in
                                      const int* bad_off, int verify, int* status, uint32_t* flags, uint32_t* crcs,
                                      void* stream) {
   if (!h || nbids < 0 || n <= 0 || (nbids > 0 && (!shards || !status || !bad_off))) return CFSEC_ERR_INVALID_ARG;
-  if (nbids > 0 && bad_off[0] != 0) return CFSEC_ERR_INVALID_ARG;
-  for (int b = 0; b < nbids; ++b)
-    if (bad_off[b + 1] < bad_off[b] || (bad_off[b + 1] > bad_off[b] && !bad_idx)) return CFSEC_ERR_INVALID_ARG;
+  if (!bad_off_valid(nbids, bad_off, bad_idx)) return CFSEC_ERR_INVALID_ARG;
   if (verify && nbids > 0 && !flags) return CFSEC_ERR_INVALID_ARG;
   cfsec::AsyncOut a;
   a.stream = as_stream(stream);
   a.flags = flags;
-  cfsec::CrcOut c;
-  c.words = crcs;
-  c.n = (size_t)nbids * n;
+  const cfsec::CrcOut c = crc_out(crcs, nbids, n);
   return guarded([&] {
     return h->e->reconstruct_batch(shards, n, nbids, bad_idx, bad_off, CFSEC_MEM_DEVICE, verify != 0, status, &a,
                                    crcs ? &c : nullptr);
@@ -531,9 +536,7 @@ int cfsec_ec_encode_batch_async(cfsec_ec* h, cfsec_shard* shards, int n, int nst
   cfsec::AsyncOut a;
   a.stream = as_stream(stream);
   a.flags = flags;
-  cfsec::CrcOut c;
-  c.words = crcs;
-  c.n = (size_t)nstripes * n;
+  const cfsec::CrcOut c = crc_out(crcs, nstripes, n);
   return guarded([&] {
     return h->e->encode_batch(shards, n, nstripes, CFSEC_MEM_DEVICE, status, &a, crcs ? &c : nullptr);
   });
@@ -591,29 +594,17 @@ int cfsec_crc32_ieee_batch(uint8_t* const* ptrs, size_t shard_size, int n, uint3
     return CFSEC_ERR_INVALID_ARG;
   }
   return guarded([&] {
-    if (device < 0 && hipGetDevice(&device) != hipSuccess) return (int)CFSEC_ERR_DEVICE;
-    cfsec::DeviceContext* ctx = cfsec::DeviceContext::get(device);
-    if (!ctx) {
-      cfsec::set_last_error("no HIP device available to the cfsec engine");
-      return (int)CFSEC_ERR_DEVICE;
-    }
-    cfsec::DeviceGuard g(device);
-    if (!g.ok()) return cfsec::hip_status(hipErrorInvalidDevice, "hipSetDevice");
-    cfsec::DeviceContext::Workspace* ws = nullptr;
-    int st = ctx->acquire(0, (size_t)n, &ws);
-    if (st != CFSEC_OK) return st;
-    hipStream_t s = stream ? as_stream(stream) : ws->stream;
-    if (!stream) st = ctx->order_after_default(ws);
-    if (st == CFSEC_OK)
-      st = cfsec::hip_status(cfsec::launch_crc32(ptrs, shard_size, n, ws->dflags, s), "launch_crc32");
-    if (st == CFSEC_OK)
-      st = cfsec::hip_status(hipMemcpyAsync(ws->hflags, ws->dflags, 4 * (size_t)n, hipMemcpyDeviceToHost, s),
-                             "hipMemcpyAsync D2H");
-    const int sync = ctx->finish(ws, s);
-    if (st == CFSEC_OK) st = sync;
+    cfsec::DeviceContext* ctx = device_context(device);
+    if (!ctx) return (int)CFSEC_ERR_DEVICE;
+    cfsec::SyncCall call(ctx, 0, (size_t)n, as_stream(stream), !stream);
+    if (!call.begun()) return call.status();
+    cfsec::DeviceContext::Workspace* ws = call.ws();
+    hipStream_t s = call.stream();
+    call.step("launch_crc32", [&] { return cfsec::launch_crc32(ptrs, shard_size, n, ws->dflags, s); });
+    call.fetch_words((size_t)n);
+    const int st = call.finish();
     if (st == CFSEC_OK)
       for (int i = 0; i < n; ++i) out[i] = cfsec::crc32_finalize(ws->hflags[i], shard_size);
-    ctx->release(ws);
     return st;
   });
 }
@@ -693,15 +684,8 @@ int cfsec_crc32block_decode_batch(const uint8_t* const* srcs, int64_t src_len, u
   if (n < 0 || size < 0 || from < 0 || from > to || to > size || (n > 0 && (!srcs || !bad)) ||
       (n > 0 && to > from && !dsts))
     return CFSEC_ERR_INVALID_ARG;
-  {  // the framed end of the last block the range touches must lie inside every source object
-    const int64_t P = block_len - 4, b0 = from / P;
-    const int64_t b1 = from < to ? (to - 1) / P : (from % P ? b0 : b0 - 1);
-    const int64_t f1 = std::min(crc32block_framed(size, block_len), (b1 + 1) * block_len);
-    if (b1 >= b0 && src_len < f1) {
-      cfsec::set_last_error("crc32block decode: framed source shorter than the blocks the range touches");
-      return CFSEC_ERR_SHORT_DATA;
-    }
-  }
+  // the framed end of the last block the range touches must lie inside every source object
+  if (decode_source_short(blocks_touched(false, size, block_len, from, to), src_len)) return CFSEC_ERR_SHORT_DATA;
   return guarded([&] {
     hipStream_t s = as_stream(stream);
     int st = CFSEC_OK;

@@ -8,8 +8,10 @@
 #include <algorithm>
 #include <cstring>
 #include <map>
+#include <optional>
 #include <shared_mutex>
 #include <unordered_map>
+#include <utility>
 
 namespace cfsec {
 
@@ -334,6 +336,40 @@ void DeviceContext::release_after(Workspace* ws, hipStream_t stream) {
   release(ws);
 }
 
+// ---------------------------------------------------------------- synchronous call scope
+
+SyncCall::SyncCall(DeviceContext* ctx, size_t bytes, size_t nflags, hipStream_t caller, bool after_default)
+    : guard_(ctx->device()), ctx_(ctx) {
+  if (!guard_.ok()) {
+    st_ = hip_status(hipErrorInvalidDevice, "hipSetDevice");
+    return;
+  }
+  st_ = ctx_->acquire(bytes, nflags, &ws_);
+  if (st_ != CFSEC_OK) return;
+  stream_ = caller ? caller : ws_->stream;
+  if (after_default) st_ = ctx_->order_after_default(ws_);
+}
+
+Status SyncCall::finish() {
+  if (!ws_ || finished_) return st_;
+  finished_ = true;
+  const std::string first = st_ != CFSEC_OK ? last_error_cstr() : "";
+  Status sync = ctx_->finish(ws_, stream_);
+  if (two_lanes_) {
+    const Status second = ctx_->finish(ws_, ws_->stream2);
+    if (sync == CFSEC_OK) sync = second;
+  }
+  if (st_ == CFSEC_OK) st_ = sync;
+  else set_last_error(first);  // a failed wait after a failed step: the step's text stays
+  return st_;
+}
+
+SyncCall::~SyncCall() {
+  if (!ws_) return;
+  finish();
+  ctx_->release(ws_);
+}
+
 // ---------------------------------------------------------------- inversion cache
 
 bool InversionCache::get(const std::vector<int>& invalid, Matrix* out) const {
@@ -382,8 +418,34 @@ Status RSEngine::create(int k, int m, int device, std::unique_ptr<RSEngine>* out
   return CFSEC_OK;
 }
 
+// crc32.ChecksumIEEE of n rows of S bytes as they stand into crcs[idx[i]] (idx null: crcs[i]), the
+// nwords words zeroed first; S == 0: the words zeroed, nothing launched (ChecksumIEEE(nil) == 0).
+static Status crc_rows_as_they_stand(const uint8_t* const* ptrs, int n, size_t S, uint32_t* crcs, size_t nwords,
+                                     const uint32_t* idx, hipStream_t stream) {
+  const Status st = hip_status(hipMemsetAsync(crcs, 0, sizeof(uint32_t) * nwords, stream), "hipMemsetAsync");
+  if (st != CFSEC_OK || S == 0) return st;
+  return hip_status(launch_crc32_to(ptrs, S, n, crcs, idx, crc32_shift_ones(S), stream), "launch_crc32_to");
+}
+
+// Product + checksums: the fused kernel where it takes the job, else the product then the
+// standalone CRC kernel over the same shards (one more read of each).
 static Status matvec_with_crc(const MatVecJob& job, uint8_t* const* ptrs, int total, const std::vector<int>& slot,
-                              size_t S, uint32_t* crcs, hipStream_t stream);
+                              size_t S, uint32_t* crcs, hipStream_t stream) {
+  if (matvec_crc_accepts(job, total, slot.data()))
+    return hip_status(launch_matvec_crc(job, crcs, total, slot.data(), stream), "launch_matvec_crc");
+  const Status st = hip_status(launch_matvec(job, stream), "launch_matvec");
+  if (st != CFSEC_OK) return st;
+  std::vector<const uint8_t*> p;
+  std::vector<uint32_t> idx;
+  const bool cin = slot[0] >= 0;
+  for (int s = 0; s < job.nstripes; ++s)
+    for (int i = 0; i < job.k + job.m; ++i) {
+      if (i < job.k && !cin) continue;
+      p.push_back(i < job.k ? job.in[(size_t)s * job.k + i] : job.out[(size_t)s * job.m + i - job.k]);
+      idx.push_back((uint32_t)(s * total + slot[i]));
+    }
+  return crc_rows_as_they_stand(p.data(), (int)p.size(), S, crcs, (size_t)total * job.nstripes, idx.data(), stream);
+}
 
 // The device address of page-locked host memory (hipHostMalloc / cfsec_host_alloc); false for
 // pageable memory.
@@ -488,6 +550,77 @@ bool device_alias(uint8_t* p, uint8_t** dptr) {
   return true;
 }
 
+// Verify with more inputs than one launch carries: computed into staging, then compared (wide_verify).
+static bool two_step_verify(MatVecMode mode, int nin) { return mode == MatVecMode::kVerify && nin > 32; }
+
+CallPath single_call_path(bool host, bool rows_aliasable, bool stage_usable, size_t moved_bytes, int nin,
+                          MatVecMode mode) {
+  if (!host) return CallPath::kInPlace;
+  if (rows_aliasable) return CallPath::kPinnedInPlace;
+  if (two_step_verify(mode, nin)) return CallPath::kStagedWhole;
+  return moved_bytes <= RSEngine::kSmallPageable && stage_usable ? CallPath::kSmallStage : CallPath::kPipeline;
+}
+
+namespace {
+std::vector<int> index_range(int a, int b) {
+  std::vector<int> v;
+  for (int i = a; i < b; ++i) v.push_back(i);
+  return v;
+}
+
+// Device addresses of n rows: device memory as is, host memory through device_alias.  False at
+// the first host row that is not page-locked (the rows from it on are left unresolved).
+bool resolve_rows(cfsec_shard* const* rows, int n, bool host, uint8_t** dptr) {
+  for (int i = 0; i < n; ++i)
+    if (!host) dptr[i] = rows[i]->data;
+    else if (!device_alias(rows[i]->data, &dptr[i])) return false;
+  return true;
+}
+
+// The two-step Verify over d (device addresses: the rows.cols inputs, then the outputs): the product
+// stored into tmp0 (a slot per output row), then compared with the outputs through an identity matrix.
+void wide_verify(SyncCall& call, const Matrix& rows, uint8_t* const* d, size_t S, uint8_t* tmp0) {
+  const int nout = rows.rows;
+  std::vector<uint8_t*> tmp(nout);
+  for (int r = 0; r < nout; ++r) tmp[r] = tmp0 + align_up(S, kSlotAlign) * r;
+  MatVecJob job = matvec_job(rows.cols, nout, rows.v.data(), S, 1, d, tmp.data());
+  job.flags = call.ws()->dflags;
+  call.step("launch_matvec", [&] { return launch_matvec(job, call.stream()); });
+  Matrix ident(nout, nout);
+  for (int r = 0; r < nout; ++r) ident.at(r, r) = 1;
+  MatVecJob cmp = matvec_job(nout, nout, ident.v.data(), S, 1, tmp.data(), d + rows.cols);
+  cmp.flags = job.flags;
+  cmp.mode = MatVecMode::kVerify;
+  call.step("launch_matvec(verify)", [&] { return launch_matvec(cmp, call.stream()); });
+}
+
+// The product of a call over rows the GPU addresses (d as above; through tmp0 when given: the wide
+// Verify), and Verify's word on its way back.
+void issue_product(SyncCall& call, const Matrix& rows, uint8_t* const* d, size_t S, MatVecMode mode, uint8_t* tmp0) {
+  const bool verify = mode == MatVecMode::kVerify;
+  DeviceContext::Workspace* ws = call.ws();
+  if (verify) call.memset(ws->dflags, 0, 4);
+  if (tmp0) {
+    wide_verify(call, rows, d, S, tmp0);
+  } else {
+    MatVecJob job = matvec_job(rows.cols, rows.rows, rows.v.data(), S, 1, d, d + rows.cols);
+    job.flags = ws->dflags;
+    job.mode = mode;
+    call.step("launch_matvec", [&] { return launch_matvec(job, call.stream()); });
+  }
+  if (verify) call.fetch_words(1);
+}
+
+// The wait of a call whose product is issued, and what Verify's word says.
+Status finish_product(SyncCall& call, MatVecMode mode, bool* ok) {
+  std::optional<HostTimer> tm("  run: finish");
+  const Status st = call.finish();
+  tm.reset();
+  if (st == CFSEC_OK && mode == MatVecMode::kVerify && ok) *ok = call.ws()->hflags[0] == 0;
+  return st;
+}
+}  // namespace
+
 Status RSEngine::run(const Matrix& rows, const std::vector<cfsec_shard*>& ins,
                      const std::vector<cfsec_shard*>& outs, size_t S, int mem, hipStream_t stream,
                      MatVecMode mode, bool* ok) {
@@ -498,147 +631,94 @@ Status RSEngine::run(const Matrix& rows, const std::vector<cfsec_shard*>& ins,
     return CFSEC_ERR_DEVICE;
   }
   if (mem != CFSEC_MEM_HOST && mem != CFSEC_MEM_DEVICE) return CFSEC_ERR_INVALID_ARG;
-  for (auto* s : ins)
+  std::vector<cfsec_shard*> all(ins);  // the call's rows: the inputs, then the outputs
+  all.insert(all.end(), outs.begin(), outs.end());
+  for (auto* s : all)
     if (!s->data) return CFSEC_ERR_INVALID_ARG;
-  for (auto* s : outs)
-    if (!s->data) return CFSEC_ERR_INVALID_ARG;
-  const int nin = (int)ins.size(), nout = (int)outs.size();
-  if (rows.rows != nout || rows.cols != nin) return CFSEC_ERR_INVALID_ARG;
+  const int nin = (int)ins.size(), n = (int)all.size();
+  if (rows.rows != n - nin || rows.cols != nin) return CFSEC_ERR_INVALID_ARG;
 
-  DeviceGuard g(ctx_->device());
-  if (!g.ok()) return hip_status(hipErrorInvalidDevice, "hipSetDevice");
-
-  const bool verify = mode == MatVecMode::kVerify;
+  // the facts: where the rows are, and for a small pageable call whether there is a stage for it
   const bool host = mem == CFSEC_MEM_HOST;
-  const size_t slot = align_up(S, kSlotAlign);
-  // Verify with more inputs than one launch carries: compute into staging, then compare.
-  const bool two_step_verify = verify && nin > 32;
+  const size_t moved = S * size_t(n);
+  std::optional<DeviceGuard> g;  // a host call's facts ask the runtime; a device call's do not
   if (host) {
-    // Page-locked buffers (cfsec_host_alloc) are device-addressable: the kernel reads and writes
-    // them over PCIe with no staging copies (tools/bench_host.py: 50.7 GB/s of data for EC12P4
-    // encode vs 32.4 through the staged pipeline and 26.7 from pageable memory).
-    std::vector<cfsec_shard> zin(nin), zout(nout);
-    bool zero_copy = true;
-    for (int i = 0; i < nin && zero_copy; ++i) {
-      zin[i] = *ins[i];
-      zero_copy = device_alias(ins[i]->data, &zin[i].data);
-    }
-    for (int r = 0; r < nout && zero_copy; ++r) {
-      zout[r] = *outs[r];
-      zero_copy = device_alias(outs[r]->data, &zout[r].data);
-    }
-    if (zero_copy) {
-      std::vector<cfsec_shard*> pin(nin), pout(nout);
-      for (int i = 0; i < nin; ++i) pin[i] = &zin[i];
-      for (int r = 0; r < nout; ++r) pout[r] = &zout[r];
-      return run(rows, pin, pout, S, CFSEC_MEM_DEVICE, nullptr, mode, ok);
-    }
-    // Small pageable calls (a degraded range read's segments): the rows copied on the CPU into
-    // page-locked staging and coded there in place, instead of HIP's staged copies of pageable memory
-    // (~130 us per call whatever the size up to 64 KiB, profiles/r06/bench_s1).
-    const size_t total = S * (size_t)(nin + nout);
-    if (!two_step_verify && total <= kSmallPageable) {
-      std::pair<uint8_t*, size_t> stage = pinned_stage_take(total);
-      // the stage's device address, resolved once: the inner call is a device-memory call on it (one
-      // level, whatever happens); a stage the GPU cannot address goes back and run_host takes the call
-      uint8_t* dstage = nullptr;
-      if (stage.first && device_alias(stage.first, &dstage)) {
-        std::vector<cfsec_shard> sin(nin), sout(nout);
-        std::vector<cfsec_shard*> pin(nin), pout(nout);
-        for (int i = 0; i < nin; ++i) {
-          std::memcpy(stage.first + S * i, ins[i]->data, S);
-          sin[i] = cfsec_shard{dstage + S * i, S, S};
-          pin[i] = &sin[i];
-        }
-        for (int r = 0; r < nout; ++r) {
-          if (mode != MatVecMode::kStore) std::memcpy(stage.first + S * (nin + r), outs[r]->data, S);
-          sout[r] = cfsec_shard{dstage + S * (nin + r), S, S};
-          pout[r] = &sout[r];
-        }
-        Status st = run(rows, pin, pout, S, CFSEC_MEM_DEVICE, nullptr, mode, ok);
-        if (st == CFSEC_OK && mode != MatVecMode::kVerify)
-          for (int r = 0; r < nout; ++r) std::memcpy(outs[r]->data, stage.first + S * (nin + r), S);
-        pinned_stage_give(stage);
-        return st;
-      }
-      pinned_stage_give(stage);
-    }
-    if (!two_step_verify) return run_host(rows, ins, outs, S, mode, ok);
+    g.emplace(ctx_->device());
+    if (!g->ok()) return hip_status(hipErrorInvalidDevice, "hipSetDevice");
   }
-  size_t staging = host ? slot * size_t(nin + nout) : 0;
-  if (two_step_verify) staging += slot * size_t(nout);
-
-  DeviceContext::Workspace* ws = nullptr;
-  std::unique_ptr<HostTimer> tm(new HostTimer("  run: acquire"));
-  Status st = ctx_->acquire(staging, 1, &ws);
-  if (st != CFSEC_OK) return st;
-  hipStream_t s = (host || !stream) ? ws->stream : stream;
-  if (!host && !stream) st = ctx_->order_after_default(ws);
-  tm.reset(new HostTimer("  run: copies + launch"));
-
-  std::vector<const uint8_t*> din(nin);
-  std::vector<uint8_t*> dout(nout);
-  for (int i = 0; i < nin; ++i) {
-    if (host) {
-      din[i] = ws->dbuf + slot * i;
-      if (st == CFSEC_OK)
-        st = hip_status(hipMemcpyAsync(const_cast<uint8_t*>(din[i]), ins[i]->data, S, hipMemcpyHostToDevice, s),
-                        "hipMemcpyAsync H2D");
-    } else {
-      din[i] = ins[i]->data;
+  std::vector<uint8_t*> d(n);
+  const bool aliasable = resolve_rows(all.data(), n, host, d.data());
+  CallPath path = single_call_path(host, aliasable, true, moved, nin, mode);
+  std::pair<uint8_t*, size_t> stage{nullptr, 0};
+  uint8_t* dstage = nullptr;
+  if (path == CallPath::kSmallStage) {
+    // the stage's device address, resolved once; a stage the GPU cannot address goes back at once
+    stage = pinned_stage_take(moved);
+    if (!stage.first || !device_alias(stage.first, &dstage)) {
+      pinned_stage_give(std::exchange(stage, {}));
+      path = single_call_path(host, aliasable, false, moved, nin, mode);
     }
   }
-  for (int r = 0; r < nout; ++r) {
-    if (host) {
-      dout[r] = ws->dbuf + slot * (nin + r);
-      if (st == CFSEC_OK && mode != MatVecMode::kStore)
-        st = hip_status(hipMemcpyAsync(dout[r], outs[r]->data, S, hipMemcpyHostToDevice, s),
-                        "hipMemcpyAsync H2D");
-    } else {
-      dout[r] = outs[r]->data;
-    }
+  Status st = CFSEC_OK;
+  switch (path) {
+    case CallPath::kInPlace: st = run_in_place(rows, d.data(), S, stream, mode, ok); break;
+    case CallPath::kPinnedInPlace: st = run_in_place(rows, d.data(), S, nullptr, mode, ok); break;
+    case CallPath::kSmallStage: st = run_small_stage(rows, all, S, mode, ok, stage.first, dstage); break;
+    case CallPath::kPipeline: st = run_host(rows, ins, outs, S, mode, ok); break;
+    case CallPath::kStagedWhole: st = run_staged_verify(rows, all, S, ok); break;
   }
-  if (st == CFSEC_OK && verify) st = hip_status(hipMemsetAsync(ws->dflags, 0, 4, s), "hipMemsetAsync");
-  if (st == CFSEC_OK) {
-    MatVecJob job = matvec_job(nin, nout, rows.v.data(), S, 1, din.data(), nullptr);
-    job.flags = ws->dflags;
-    if (!two_step_verify) {
-      job.out = dout.data();
-      job.mode = mode;
-      st = hip_status(launch_matvec(job, s), "launch_matvec");
-    } else {
-      uint8_t* tmp0 = ws->dbuf + (host ? slot * size_t(nin + nout) : 0);
-      std::vector<uint8_t*> tmp(nout);
-      for (int r = 0; r < nout; ++r) tmp[r] = tmp0 + slot * r;
-      job.out = tmp.data();
-      job.mode = MatVecMode::kStore;
-      st = hip_status(launch_matvec(job, s), "launch_matvec");
-      if (st == CFSEC_OK) {
-        Matrix ident(nout, nout);
-        for (int r = 0; r < nout; ++r) ident.at(r, r) = 1;
-        std::vector<const uint8_t*> tin(tmp.begin(), tmp.end());
-        MatVecJob cmp = job;
-        cmp.k = nout;
-        cmp.coef = ident.v.data();
-        cmp.in = tin.data();
-        cmp.out = dout.data();
-        cmp.mode = MatVecMode::kVerify;
-        st = hip_status(launch_matvec(cmp, s), "launch_matvec(verify)");
-      }
-    }
-  }
-  if (st == CFSEC_OK && verify)
-    st = hip_status(hipMemcpyAsync(ws->hflags, ws->dflags, 4, hipMemcpyDeviceToHost, s), "hipMemcpyAsync D2H");
-  if (st == CFSEC_OK && host && !verify)
-    for (int r = 0; r < nout && st == CFSEC_OK; ++r)
-      st = hip_status(hipMemcpyAsync(outs[r]->data, dout[r], S, hipMemcpyDeviceToHost, s), "hipMemcpyAsync D2H");
-  tm.reset(new HostTimer("  run: finish"));
-  const Status sync = ctx_->finish(ws, s);
-  tm.reset();
-  if (st == CFSEC_OK) st = sync;
-  if (st == CFSEC_OK && verify && ok) *ok = ws->hflags[0] == 0;
-  ctx_->release(ws);
+  pinned_stage_give(stage);
   return st;
+}
+
+// Page-locked buffers (cfsec_host_alloc) are device-addressable: the kernel reads and writes them
+// over PCIe with no staging copies (tools/bench_host.py: 50.7 GB/s of data for EC12P4 encode vs
+// 32.4 through the staged pipeline and 26.7 from pageable memory).  A NULL stream: the call runs on
+// the workspace's stream, ordered after the legacy default stream.
+Status RSEngine::run_in_place(const Matrix& rows, uint8_t* const* d, size_t S, hipStream_t stream, MatVecMode mode,
+                              bool* ok) {
+  const bool wide = two_step_verify(mode, rows.cols);
+  std::unique_ptr<HostTimer> tm(new HostTimer("  run: acquire"));
+  SyncCall call(ctx_, wide ? align_up(S, kSlotAlign) * size_t(rows.rows) : 0, 1, stream, !stream);
+  if (!call.begun()) return call.status();
+  tm.reset(new HostTimer("  run: copies + launch"));
+  issue_product(call, rows, d, S, mode, wide ? call.ws()->dbuf : nullptr);
+  tm.reset();
+  return finish_product(call, mode, ok);
+}
+
+// Small pageable calls (a degraded range read's segments): the rows copied on the CPU into
+// page-locked staging and coded there in place, instead of HIP's staged copies of pageable memory
+// (~130 us per call whatever the size up to 64 KiB, profiles/r06/bench_s1).
+Status RSEngine::run_small_stage(const Matrix& rows, const std::vector<cfsec_shard*>& all, size_t S, MatVecMode mode,
+                                 bool* ok, uint8_t* stage, uint8_t* dstage) {
+  const int nin = rows.cols, n = (int)all.size();
+  std::vector<uint8_t*> d(n);
+  for (int i = 0; i < n; ++i) {
+    if (i < nin || mode != MatVecMode::kStore) std::memcpy(stage + S * i, all[i]->data, S);
+    d[i] = dstage + S * i;
+  }
+  const Status st = run_in_place(rows, d.data(), S, nullptr, mode, ok);
+  if (st == CFSEC_OK && mode != MatVecMode::kVerify)
+    for (int i = nin; i < n; ++i) std::memcpy(all[i]->data, stage + S * i, S);
+  return st;
+}
+
+Status RSEngine::run_staged_verify(const Matrix& rows, const std::vector<cfsec_shard*>& all, size_t S, bool* ok) {
+  const int n = (int)all.size();
+  const size_t slot = align_up(S, kSlotAlign);
+  std::unique_ptr<HostTimer> tm(new HostTimer("  run: acquire"));
+  SyncCall call(ctx_, slot * size_t(n + rows.rows), 1, nullptr, false);
+  if (!call.begun()) return call.status();
+  tm.reset(new HostTimer("  run: copies + launch"));
+  std::vector<uint8_t*> d(n);
+  for (int i = 0; i < n; ++i) {
+    d[i] = call.ws()->dbuf + slot * i;
+    call.copy(d[i], all[i]->data, S, hipMemcpyHostToDevice);
+  }
+  issue_product(call, rows, d.data(), S, MatVecMode::kVerify, call.ws()->dbuf + slot * size_t(n));
+  tm.reset();
+  return finish_product(call, MatVecMode::kVerify, ok);
 }
 
 namespace {
@@ -685,49 +765,41 @@ Status RSEngine::run_host(const Matrix& rows, const std::vector<cfsec_shard*>& i
   const size_t nchunks = (S + chunk - 1) / chunk;
   const int nlanes = nchunks > 1 ? 2 : 1;
   const size_t per_lane = chunk * size_t(nin + nout);
-  DeviceContext::Workspace* ws = nullptr;
-  Status st = ctx_->acquire(per_lane * nlanes, 1, &ws);
-  if (st != CFSEC_OK) return st;
-  hipStream_t lane[2] = {ws->stream, ws->stream2};
+  SyncCall call(ctx_, per_lane * nlanes, 1, nullptr, false);
+  if (!call.begun()) return call.status();
+  DeviceContext::Workspace* ws = call.ws();
+  hipStream_t lane[2] = {call.stream(), nlanes > 1 ? call.second_lane() : nullptr};
   const int64_t in_stride = host_row_stride(ins), out_stride = host_row_stride(outs);
   if (verify) {
-    st = hip_status(hipMemsetAsync(ws->dflags, 0, 4, lane[0]), "hipMemsetAsync");
-    if (st == CFSEC_OK && nlanes > 1) st = lane_wait(ws->ev, lane[0], lane[1]);
+    call.memset(ws->dflags, 0, 4);
+    if (nlanes > 1) call.step("lane_wait", [&] { return lane_wait(ws->ev, lane[0], lane[1]); });
   }
-  std::vector<const uint8_t*> din(nin);
-  std::vector<uint8_t*> dout(nout);
-  for (size_t j = 0; j < nchunks && st == CFSEC_OK; ++j) {
+  std::vector<uint8_t*> d(nin + nout);  // a chunk's rows in its lane: the inputs, then the outputs
+  for (size_t j = 0; j < nchunks && call.ok(); ++j) {
     const int l = (int)(j % nlanes);
     hipStream_t s = lane[l];
     uint8_t* base = ws->dbuf + per_lane * l;
     const size_t off = j * chunk, len = std::min(chunk, S - off);
-    for (int i = 0; i < nin; ++i) din[i] = base + chunk * i;
-    for (int r = 0; r < nout; ++r) dout[r] = base + chunk * (nin + r);
-    st = hip_status(copy_rows(ins, in_stride, off, len, base, chunk, true, s), "hipMemcpyAsync H2D");
-    if (st == CFSEC_OK && verify)
-      st = hip_status(copy_rows(outs, out_stride, off, len, base + chunk * nin, chunk, true, s), "hipMemcpyAsync H2D");
-    if (st == CFSEC_OK) {
-      MatVecJob job = matvec_job(nin, nout, rows.v.data(), len, 1, din.data(), dout.data());
-      job.mode = mode;
-      job.flags = ws->dflags;
-      st = hip_status(launch_matvec(job, s), "launch_matvec");
-    }
-    if (st == CFSEC_OK && !verify)
-      st = hip_status(copy_rows(outs, out_stride, off, len, base + chunk * nin, chunk, false, s), "hipMemcpyAsync D2H");
+    for (int i = 0; i < nin + nout; ++i) d[i] = base + chunk * i;
+    MatVecJob job = matvec_job(nin, nout, rows.v.data(), len, 1, d.data(), d.data() + nin);
+    job.mode = mode;
+    job.flags = ws->dflags;
+    // the outputs: in before a Verify's launch, out after any other
+    const auto out_rows = [&] { return copy_rows(outs, out_stride, off, len, base + chunk * nin, chunk, verify, s); };
+    call.step("hipMemcpyAsync H2D", [&] { return copy_rows(ins, in_stride, off, len, base, chunk, true, s); });
+    if (verify) call.step("hipMemcpyAsync H2D", out_rows);
+    call.step("launch_matvec", [&] { return launch_matvec(job, s); });
+    if (!verify) call.step("hipMemcpyAsync D2H", out_rows);
   }
-  if (st == CFSEC_OK && verify && nlanes > 1) st = lane_wait(ws->ev, lane[1], lane[0]);
-  if (st == CFSEC_OK && verify)
-    st = hip_status(hipMemcpyAsync(ws->hflags, ws->dflags, 4, hipMemcpyDeviceToHost, lane[0]), "hipMemcpyAsync D2H");
-  for (int l = 0; l < nlanes; ++l) {
-    const Status sync = ctx_->finish(ws, lane[l]);
-    if (st == CFSEC_OK) st = sync;
-  }
+  if (verify && nlanes > 1) call.step("lane_wait", [&] { return lane_wait(ws->ev, lane[1], lane[0]); });
+  if (verify) call.fetch_words(1);
+  const Status st = call.finish();
   if (st == CFSEC_OK && verify && ok) *ok = ws->hflags[0] == 0;
-  ctx_->release(ws);
   return st;
 }
 
-Status RSEngine::encode(cfsec_shard* shards, int n, int mem, hipStream_t stream) {
+// Encode (kStore) and Verify (kVerify): the parity rows over the whole stripe.
+Status RSEngine::code_stripe(cfsec_shard* shards, int n, int mem, hipStream_t stream, MatVecMode mode, bool* ok) {
   if (!shards || n != total()) return CFSEC_ERR_TOO_FEW_SHARDS;
   size_t S = 0;
   Status st = check_shards(shards, n, false, &S);
@@ -735,7 +807,11 @@ Status RSEngine::encode(cfsec_shard* shards, int n, int mem, hipStream_t stream)
   std::vector<cfsec_shard*> ins, outs;
   for (int i = 0; i < k_; ++i) ins.push_back(&shards[i]);
   for (int i = k_; i < n; ++i) outs.push_back(&shards[i]);
-  return run(parity_, ins, outs, S, mem, stream, MatVecMode::kStore, nullptr);
+  return run(parity_, ins, outs, S, mem, stream, mode, ok);
+}
+
+Status RSEngine::encode(cfsec_shard* shards, int n, int mem, hipStream_t stream) {
+  return code_stripe(shards, n, mem, stream, MatVecMode::kStore, nullptr);
 }
 
 Status RSEngine::encode_crc(cfsec_shard* shards, int n, int mem, hipStream_t stream, uint32_t* crcs) {
@@ -751,62 +827,44 @@ Status RSEngine::encode_crc(cfsec_shard* shards, int n, int mem, hipStream_t str
   if (mem != CFSEC_MEM_HOST && mem != CFSEC_MEM_DEVICE) return CFSEC_ERR_INVALID_ARG;
   for (int i = 0; i < n; ++i)
     if (!shards[i].data) return CFSEC_ERR_INVALID_ARG;
-  DeviceGuard g(ctx_->device());
-  if (!g.ok()) return hip_status(hipErrorInvalidDevice, "hipSetDevice");
   // device addresses of the shards: device memory as is, pinned host pages aliased (zero-copy),
   // pageable host memory staged whole through the workspace
-  std::vector<uint8_t*> dptr(n);
-  bool staged = false;
-  if (mem == CFSEC_MEM_HOST)
-    for (int i = 0; i < n && !staged; ++i) staged = !device_alias(shards[i].data, &dptr[i]);
-  else
-    for (int i = 0; i < n; ++i) dptr[i] = shards[i].data;
-  const size_t slot = align_up(S, kSlotAlign);
-  DeviceContext::Workspace* ws = nullptr;
-  st = ctx_->acquire(staged ? slot * n : 0, (size_t)n, &ws);
-  if (st != CFSEC_OK) return st;
-  hipStream_t s = (mem == CFSEC_MEM_HOST || !stream) ? ws->stream : stream;
-  if (!staged && !stream) st = ctx_->order_after_default(ws);
-  if (staged)
-    for (int i = 0; i < n; ++i) {
-      dptr[i] = ws->dbuf + slot * i;
-      if (i < k_ && st == CFSEC_OK)
-        st = hip_status(hipMemcpyAsync(dptr[i], shards[i].data, S, hipMemcpyHostToDevice, s), "hipMemcpyAsync H2D");
-    }
-  if (st == CFSEC_OK && m_ > 0) {
-    std::vector<const uint8_t*> in(dptr.begin(), dptr.begin() + k_);
-    const MatVecJob job = matvec_job(k_, m_, parity_.v.data(), S, 1, in.data(), dptr.data() + k_);
-    std::vector<int> slots(n);
-    for (int i = 0; i < n; ++i) slots[i] = i;
-    st = matvec_with_crc(job, dptr.data(), n, slots, S, ws->dflags, s);
-  } else if (st == CFSEC_OK) {
-    st = hip_status(hipMemsetAsync(ws->dflags, 0, 4 * (size_t)n, s), "hipMemsetAsync");
-    std::vector<const uint8_t*> p(dptr.begin(), dptr.end());
-    if (st == CFSEC_OK)
-      st = hip_status(launch_crc32_to(p.data(), S, n, ws->dflags, nullptr, crc32_shift_ones(S), s), "launch_crc32_to");
+  const bool host = mem == CFSEC_MEM_HOST;
+  std::optional<DeviceGuard> g;
+  if (host) {
+    g.emplace(ctx_->device());
+    if (!g->ok()) return hip_status(hipErrorInvalidDevice, "hipSetDevice");
   }
-  if (st == CFSEC_OK && staged)
-    for (int r = k_; r < n && st == CFSEC_OK; ++r)
-      st = hip_status(hipMemcpyAsync(shards[r].data, dptr[r], S, hipMemcpyDeviceToHost, s), "hipMemcpyAsync D2H");
-  if (st == CFSEC_OK)
-    st = hip_status(hipMemcpyAsync(ws->hflags, ws->dflags, 4 * (size_t)n, hipMemcpyDeviceToHost, s), "hipMemcpyAsync D2H");
-  const Status sync = ctx_->finish(ws, s);
-  if (st == CFSEC_OK) st = sync;
+  std::vector<cfsec_shard*> all(n);
+  for (int i = 0; i < n; ++i) all[i] = &shards[i];
+  std::vector<uint8_t*> dptr(n);
+  const bool staged = !resolve_rows(all.data(), n, host, dptr.data());
+  const size_t slot = align_up(S, kSlotAlign);
+  SyncCall call(ctx_, staged ? slot * n : 0, (size_t)n, host ? nullptr : stream, !staged && !stream);
+  if (!call.begun()) return call.status();
+  DeviceContext::Workspace* ws = call.ws();
+  hipStream_t s = call.stream();
+  for (int i = 0; i < n && staged; ++i) {
+    dptr[i] = ws->dbuf + slot * i;
+    if (i < k_) call.copy(dptr[i], shards[i].data, S, hipMemcpyHostToDevice);
+  }
+  if (m_ > 0) {
+    const MatVecJob job = matvec_job(k_, m_, parity_.v.data(), S, 1, dptr.data(), dptr.data() + k_);
+    const std::vector<int> every = index_range(0, n);
+    call.step("matvec_with_crc", [&] { return matvec_with_crc(job, dptr.data(), n, every, S, ws->dflags, s); });
+  } else {
+    call.step("crc", [&] { return crc_rows_as_they_stand(dptr.data(), n, S, ws->dflags, (size_t)n, nullptr, s); });
+  }
+  for (int r = k_; r < n && staged; ++r) call.copy(shards[r].data, dptr[r], S, hipMemcpyDeviceToHost);
+  call.fetch_words((size_t)n);
+  st = call.finish();
   if (st == CFSEC_OK) std::memcpy(crcs, ws->hflags, 4 * (size_t)n);
-  ctx_->release(ws);
   return st;
 }
 
 Status RSEngine::verify(cfsec_shard* shards, int n, int mem, hipStream_t stream, bool* ok) {
   *ok = false;
-  if (!shards || n != total()) return CFSEC_ERR_TOO_FEW_SHARDS;
-  size_t S = 0;
-  Status st = check_shards(shards, n, false, &S);
-  if (st != CFSEC_OK) return st;
-  std::vector<cfsec_shard*> ins, outs;
-  for (int i = 0; i < k_; ++i) ins.push_back(&shards[i]);
-  for (int i = k_; i < n; ++i) outs.push_back(&shards[i]);
-  return run(parity_, ins, outs, S, mem, stream, MatVecMode::kVerify, ok);
+  return code_stripe(shards, n, mem, stream, MatVecMode::kVerify, ok);
 }
 
 Status RSEngine::plan_reconstruct(const std::vector<bool>& present, bool data_only, ReconPlan* plan) {
@@ -960,12 +1018,6 @@ struct PtrTables {
   std::vector<uint8_t*> out;
 };
 
-std::vector<int> index_range(int a, int b) {
-  std::vector<int> v;
-  for (int i = a; i < b; ++i) v.push_back(i);
-  return v;
-}
-
 // The in / out tables of a launch: the rows in_idx, then out_idx, of every stripe.
 PtrTables ptr_tables(uint8_t* const* ptrs, size_t width, int nstripes, const std::vector<int>& in_idx,
                      const std::vector<int>& out_idx) {
@@ -978,13 +1030,25 @@ PtrTables ptr_tables(uint8_t* const* ptrs, size_t width, int nstripes, const std
   return t;
 }
 
-// present[i] = shard i is not among erased[0 .. nerased); false for an index outside [0, total).
-bool parse_erased(const int* erased, int nerased, int total, std::vector<bool>* present) {
-  present->assign(total, true);
+// The erasure set of a pointer batch: present[i] = shard i is not among erased[0 .. nerased), np of
+// them present, dp of those data shards.
+struct Erasures {
+  std::vector<bool> present;
+  int np = 0, dp = 0;
+};
+
+// False for an index outside [0, total).
+bool parse_erased(const int* erased, int nerased, int total, int k, Erasures* e) {
+  e->present.assign(total, true);
   for (int i = 0; i < nerased; ++i) {
     if (erased[i] < 0 || erased[i] >= total) return false;
-    (*present)[erased[i]] = false;
+    e->present[erased[i]] = false;
   }
+  for (int i = 0; i < total; ++i)
+    if (e->present[i]) {
+      ++e->np;
+      if (i < k) ++e->dp;
+    }
   return true;
 }
 }  // namespace
@@ -1031,18 +1095,12 @@ Status RSEngine::reconstruct_batch(uint8_t* const* ptrs, size_t S, int nstripes,
                                    int nerased, bool data_only, hipStream_t stream) {
   if (!ctx_) return CFSEC_ERR_DEVICE;
   if (!ptrs || nstripes < 0 || nerased < 0 || (nerased > 0 && !erased)) return CFSEC_ERR_INVALID_ARG;
-  std::vector<bool> present;
-  if (!parse_erased(erased, nerased, total(), &present)) return CFSEC_ERR_INVALID_ARG;
-  int np = 0, dp = 0;
-  for (int i = 0; i < total(); ++i)
-    if (present[i]) {
-      ++np;
-      if (i < k_) ++dp;
-    }
-  if (np == total() || (data_only && dp == k_) || nstripes == 0 || S == 0) return CFSEC_OK;
-  if (np < k_) return CFSEC_ERR_TOO_FEW_SHARDS;
+  Erasures e;
+  if (!parse_erased(erased, nerased, total(), k_, &e)) return CFSEC_ERR_INVALID_ARG;
+  if (e.np == total() || (data_only && e.dp == k_) || nstripes == 0 || S == 0) return CFSEC_OK;
+  if (e.np < k_) return CFSEC_ERR_TOO_FEW_SHARDS;
   ReconPlan plan;
-  Status st = plan_reconstruct(present, data_only, &plan);
+  Status st = plan_reconstruct(e.present, data_only, &plan);
   if (st != CFSEC_OK) return st;
   const PtrTables t = ptr_tables(ptrs, total(), nstripes, plan.valid, plan.outputs);
   DeviceGuard g(ctx_->device());
@@ -1052,29 +1110,6 @@ Status RSEngine::reconstruct_batch(uint8_t* const* ptrs, size_t S, int nstripes,
   return hip_status(launch_matvec(job, stream), "launch_matvec(reconstruct_batch)");
 }
 
-// Product + checksums: the fused kernel where it takes the job, else the product then the
-// standalone CRC kernel over the same shards (one more read of each).
-static Status matvec_with_crc(const MatVecJob& job, uint8_t* const* ptrs, int total, const std::vector<int>& slot,
-                              size_t S, uint32_t* crcs, hipStream_t stream) {
-  if (matvec_crc_accepts(job, total, slot.data()))
-    return hip_status(launch_matvec_crc(job, crcs, total, slot.data(), stream), "launch_matvec_crc");
-  Status st = hip_status(launch_matvec(job, stream), "launch_matvec");
-  if (st != CFSEC_OK) return st;
-  st = hip_status(hipMemsetAsync(crcs, 0, sizeof(uint32_t) * (size_t)total * job.nstripes, stream), "hipMemsetAsync");
-  if (st != CFSEC_OK || S == 0) return st;
-  std::vector<const uint8_t*> p;
-  std::vector<uint32_t> idx;
-  const bool cin = slot[0] >= 0;
-  for (int s = 0; s < job.nstripes; ++s)
-    for (int i = 0; i < job.k + job.m; ++i) {
-      if (i < job.k && !cin) continue;
-      p.push_back(i < job.k ? job.in[(size_t)s * job.k + i] : job.out[(size_t)s * job.m + i - job.k]);
-      idx.push_back((uint32_t)(s * total + slot[i]));
-    }
-  return hip_status(launch_crc32_to(p.data(), S, (int)p.size(), crcs, idx.data(), crc32_shift_ones(S), stream),
-                    "launch_crc32_to");
-}
-
 Status RSEngine::encode_crc_batch(uint8_t* const* ptrs, size_t S, int nstripes, uint32_t* crcs,
                                   hipStream_t stream) {
   if (!ctx_) return CFSEC_ERR_DEVICE;
@@ -1082,13 +1117,8 @@ Status RSEngine::encode_crc_batch(uint8_t* const* ptrs, size_t S, int nstripes, 
   if (nstripes == 0) return CFSEC_OK;
   DeviceGuard g(ctx_->device());
   if (!g.ok()) return hip_status(hipErrorInvalidDevice, "hipSetDevice");
-  if (m_ == 0 || S == 0) {
-    Status st = hip_status(hipMemsetAsync(crcs, 0, 4 * (size_t)total() * nstripes, stream), "hipMemsetAsync");
-    if (st != CFSEC_OK || S == 0) return st;
-    std::vector<const uint8_t*> p(ptrs, ptrs + (size_t)total() * nstripes);
-    return hip_status(launch_crc32_to(p.data(), S, (int)p.size(), crcs, nullptr, crc32_shift_ones(S), stream),
-                      "launch_crc32_to");
-  }
+  const size_t nwords = (size_t)total() * nstripes;
+  if (m_ == 0 || S == 0) return crc_rows_as_they_stand(ptrs, (int)nwords, S, crcs, nwords, nullptr, stream);
   const PtrTables t = ptr_tables(ptrs, total(), nstripes, index_range(0, k_), index_range(k_, total()));
   const MatVecJob job = matvec_job(k_, m_, parity_.v.data(), S, nstripes, t.in.data(), t.out.data());
   return matvec_with_crc(job, ptrs, total(), index_range(0, total()), S, crcs, stream);
@@ -1098,17 +1128,15 @@ Status RSEngine::reconstruct_crc_batch(uint8_t* const* ptrs, size_t S, int nstri
                                        int nerased, bool data_only, uint32_t* crcs, hipStream_t stream) {
   if (!ctx_) return CFSEC_ERR_DEVICE;
   if (!ptrs || !crcs || nstripes < 0 || nerased < 0 || (nerased > 0 && !erased)) return CFSEC_ERR_INVALID_ARG;
-  std::vector<bool> present;
-  if (!parse_erased(erased, nerased, total(), &present)) return CFSEC_ERR_INVALID_ARG;
-  int np = 0;
-  for (int i = 0; i < total(); ++i) np += present[i] ? 1 : 0;
-  if (np < k_ && nstripes > 0) return CFSEC_ERR_TOO_FEW_SHARDS;
+  Erasures e;
+  if (!parse_erased(erased, nerased, total(), k_, &e)) return CFSEC_ERR_INVALID_ARG;
+  if (e.np < k_ && nstripes > 0) return CFSEC_ERR_TOO_FEW_SHARDS;
   DeviceGuard g(ctx_->device());
   if (!g.ok()) return hip_status(hipErrorInvalidDevice, "hipSetDevice");
   if (nstripes == 0) return CFSEC_OK;
   ReconPlan plan;
-  if (np < total()) {
-    Status st = plan_reconstruct(present, data_only, &plan);
+  if (e.np < total()) {
+    Status st = plan_reconstruct(e.present, data_only, &plan);
     if (st != CFSEC_OK) return st;
   }
   const int nout = (int)plan.outputs.size();
@@ -1125,31 +1153,25 @@ Status RSEngine::repair_crc_batch(uint8_t* const* ptrs, size_t S, int nstripes, 
                                   uint32_t* flags, uint32_t* crcs, hipStream_t stream) {
   if (!ptrs || !crcs || !flags || nstripes < 0 || nerased < 0 || (nerased > 0 && !erased))
     return CFSEC_ERR_INVALID_ARG;
-  std::vector<bool> present;
-  if (!parse_erased(erased, nerased, total(), &present)) return CFSEC_ERR_INVALID_ARG;
+  Erasures e;
+  if (!parse_erased(erased, nerased, total(), k_, &e)) return CFSEC_ERR_INVALID_ARG;
   if (!ctx_) return CFSEC_ERR_DEVICE;
-  int np = 0;
-  for (int i = 0; i < total(); ++i) np += present[i] ? 1 : 0;
-  if (np < k_ && nstripes > 0) return CFSEC_ERR_TOO_FEW_SHARDS;
+  if (e.np < k_ && nstripes > 0) return CFSEC_ERR_TOO_FEW_SHARDS;
   if (k_ > kLaunchMaxRows) return CFSEC_ERR_NOT_SUPPORTED;  // compared rows over more inputs than a launch carries
   DeviceGuard g(ctx_->device());
   if (!g.ok()) return hip_status(hipErrorInvalidDevice, "hipSetDevice");
   if (nstripes == 0) return CFSEC_OK;
-  if (S == 0) return hip_status(hipMemsetAsync(crcs, 0, 4 * (size_t)total() * nstripes, stream), "hipMemsetAsync");
+  const size_t nwords = (size_t)total() * nstripes;
+  if (S == 0) return crc_rows_as_they_stand(ptrs, (int)nwords, S, crcs, nwords, nullptr, stream);
   // the batch layer's plan of a bid: the first k present shards in, the missing ones stored, every
   // other present parity shard compared -- each shard exactly once
   StripePlan plan;
-  const Status st = plan_stripe(present, true, &plan, nullptr);
+  const Status st = plan_stripe(e.present, true, &plan, nullptr);
   if (st != CFSEC_OK) return st;
   const int nout = (int)plan.out.size();
   if (nout > kLaunchMaxRows && plan.nstore > 0 && plan.nstore < nout) return CFSEC_ERR_NOT_SUPPORTED;
-  if (nout == 0) {  // no parity shards: nothing to rebuild or compare
-    Status z = hip_status(hipMemsetAsync(crcs, 0, 4 * (size_t)total() * nstripes, stream), "hipMemsetAsync");
-    if (z != CFSEC_OK) return z;
-    std::vector<const uint8_t*> p(ptrs, ptrs + (size_t)total() * nstripes);
-    return hip_status(launch_crc32_to(p.data(), S, (int)p.size(), crcs, nullptr, crc32_shift_ones(S), stream),
-                      "launch_crc32_to");
-  }
+  // no parity shards: nothing to rebuild or compare
+  if (nout == 0) return crc_rows_as_they_stand(ptrs, (int)nwords, S, crcs, nwords, nullptr, stream);
   const PtrTables t = ptr_tables(ptrs, total(), nstripes, plan.in, plan.out);
   MatVecJob job = matvec_job(k_, nout, plan.rows.v.data(), S, nstripes, t.in.data(), t.out.data());
   if (plan.nstore < nout) {
@@ -1215,17 +1237,19 @@ Status ECEncoder::create(const cfsec_tactic& t, bool enable_verify, int concurre
   return CFSEC_OK;
 }
 
+// Encode, then with EnableVerify the Verify of what it wrote: CFSEC_ERR_VERIFY when that is false
+// (encoder.go:114-131).
+static Status encode_checked(RSEngine* e, cfsec_shard* shards, int n, int mem, hipStream_t s, bool verify) {
+  Status st = e->encode(shards, n, mem, s);
+  if (st != CFSEC_OK || !verify) return st;
+  bool ok = false;
+  st = e->verify(shards, n, mem, s, &ok);
+  return st != CFSEC_OK ? st : ok ? CFSEC_OK : CFSEC_ERR_VERIFY;
+}
+
 Status ECEncoder::encode(cfsec_shard* shards, int n, int mem, hipStream_t s) {
-  Slot slot(pool_.get());  // encoder.go:114-131
-  Status st = engine_->encode(shards, n, mem, s);
-  if (st != CFSEC_OK) return st;
-  if (enable_verify_) {
-    bool ok = false;
-    st = engine_->verify(shards, n, mem, s, &ok);
-    if (st != CFSEC_OK) return st;
-    if (!ok) return CFSEC_ERR_VERIFY;
-  }
-  return CFSEC_OK;
+  Slot slot(pool_.get());
+  return encode_checked(engine_.get(), shards, n, mem, s, enable_verify_);
 }
 
 Status ECEncoder::verify(cfsec_shard* shards, int n, int mem, hipStream_t s, bool* ok) {
@@ -1347,24 +1371,13 @@ Status LrcEncoder::encode_stripe(cfsec_shard* shards, int n, int mem, hipStream_
     // The reference's sequence, step by step: global parity (+ Verify), then every AZ's local
     // task -- task.Run lets each goroutine finish, so the AZs that pass checkShards are encoded
     // -- and the first error in AZ order (oracle/ec_oracle.py: ECOracle.encode).
-    st = engine_->encode(shards, N + M, mem, s);
+    st = encode_checked(engine_.get(), shards, N + M, mem, s, enable_verify_);
     if (st != CFSEC_OK) return st;
-    if (enable_verify_) {
-      bool ok = false;
-      st = engine_->verify(shards, N + M, mem, s, &ok);
-      if (st != CFSEC_OK) return st;
-      if (!ok) return CFSEC_ERR_VERIFY;
-    }
     Status first = CFSEC_OK;
     for (int a = 0; a < t_.az_count; ++a) {
       std::vector<cfsec_shard> ls;
       for (int g : shards_in_idc(a)) ls.push_back(shards[g]);
-      Status e = local_->encode(ls.data(), (int)ls.size(), mem, s);
-      if (e == CFSEC_OK && enable_verify_) {
-        bool ok = false;
-        e = local_->verify(ls.data(), (int)ls.size(), mem, s, &ok);
-        if (e == CFSEC_OK && !ok) e = CFSEC_ERR_VERIFY;
-      }
+      const Status e = encode_checked(local_.get(), ls.data(), (int)ls.size(), mem, s, enable_verify_);
       if (first == CFSEC_OK) first = e;
     }
     return first;

@@ -156,6 +156,70 @@ class DeviceGuard {
   bool ok_ = false;
 };
 
+// One synchronous call's round trip on a device: the DeviceGuard, a checked-out workspace, the
+// call's stream (a second lane on request), a sticky status, the wait, the release.  Every
+// single-stripe entry point runs on one (RSEngine::run's legs, run_host, encode_crc, the crc32block
+// and CRC32 calls of capi.cpp); the batch calls have BatchRun (batch.cpp).  The rules:
+//   * First error wins.  step() issues nothing once a step has failed; the call returns the first
+//     failing step's status and its set_last_error text.  (step takes the work as a callable: an
+//     argument of type hipError_t would have been issued before step could decline it.)
+//   * Always finish before release.  finish() waits on every stream the call used, after a failed
+//     step too, and the destructor finishes (if the caller has not) before the workspace goes back.
+//     Only a call that never began -- the guard or acquire failed: begun() false, status() says
+//     why -- returns early with nothing to wait for.
+//   * Words only after a good finish.  ws()->hflags is read only after finish() gave CFSEC_OK.
+//   * The stream is an argument.  `caller` non-null: the call runs on it; null: on the workspace's
+//     own non-blocking stream.  after_default: that stream is first ordered after the legacy default
+//     stream (order_after_default).  Which site passes what:
+//       run's in-place leg   caller's stream (device memory) / null (host rows in place), after_default = null stream
+//       run's staged Verify  null, never ordered;  run_host: null + second_lane(), never ordered
+//       encode_crc           as run;  after_default = nothing staged and the caller's stream is null
+//       crc32block call      caller's stream even for host memory;  after_default = null stream, nothing staged
+//       CRC32 batch          caller's stream;  after_default = null stream
+class SyncCall {
+ public:
+  SyncCall(DeviceContext* ctx, size_t bytes, size_t nflags, hipStream_t caller, bool after_default);
+  ~SyncCall();
+  SyncCall(const SyncCall&) = delete;
+  SyncCall& operator=(const SyncCall&) = delete;
+  bool begun() const { return ws_ != nullptr; }
+  bool ok() const { return st_ == CFSEC_OK; }
+  Status status() const { return st_; }
+  DeviceContext::Workspace* ws() const { return ws_; }
+  hipStream_t stream() const { return stream_; }
+  // the workspace's second stream (run_host's other lane); finish() then waits on it too
+  hipStream_t second_lane() {
+    two_lanes_ = true;
+    return ws_->stream2;
+  }
+  // issue() returns a hipError_t (reported as `what`) or a Status whose error text is already set
+  template <class F>
+  bool step(const char* what, F&& issue) {
+    if (st_ == CFSEC_OK) st_ = as_status(issue(), what);
+    return st_ == CFSEC_OK;
+  }
+  // the usual steps, on the call's stream; fetch_words: the first n flag words to their pinned mirror
+  bool copy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    return step(kind == hipMemcpyHostToDevice ? "hipMemcpyAsync H2D" : "hipMemcpyAsync D2H",
+                [&] { return hipMemcpyAsync(dst, src, bytes, kind, stream_); });
+  }
+  bool memset(void* p, int value, size_t bytes) {
+    return step("hipMemsetAsync", [&] { return hipMemsetAsync(p, value, bytes, stream_); });
+  }
+  bool fetch_words(size_t n) { return copy(ws_->hflags, ws_->dflags, 4 * n, hipMemcpyDeviceToHost); }
+  Status finish();
+
+ private:
+  static Status as_status(hipError_t e, const char* what) { return hip_status(e, what); }
+  static Status as_status(Status st, const char*) { return st; }
+  DeviceGuard guard_;
+  DeviceContext* ctx_;
+  DeviceContext::Workspace* ws_ = nullptr;
+  hipStream_t stream_ = nullptr;
+  Status st_ = CFSEC_OK;
+  bool two_lanes_ = false, finished_ = false;
+};
+
 // KRS/inversion_tree.go:16-164: decode matrices keyed by the invalid indices seen
 // before k valid rows were found; RW-locked for concurrent readers.
 class InversionCache {
@@ -381,8 +445,21 @@ class RSEngine {
   static constexpr size_t kSmallPageable = 1 << 20;
 
  private:
+  Status code_stripe(cfsec_shard* shards, int n, int mem, hipStream_t stream, MatVecMode mode, bool* ok);
+  // The legs of run, one per CallPath (single_call_path below); a call's rows are its rows.cols
+  // inputs, then its rows.rows outputs.  kInPlace / kPinnedInPlace: d holds the rows' device addresses
+  // (device memory, aliases of page-locked host rows).
+  Status run_in_place(const Matrix& rows, uint8_t* const* d, size_t S, hipStream_t stream, MatVecMode mode,
+                      bool* ok);
+  // kSmallStage: the rows copied on the CPU into the page-locked `stage` (device address dstage),
+  // coded there in place, the outputs copied back
+  Status run_small_stage(const Matrix& rows, const std::vector<cfsec_shard*>& all, size_t S, MatVecMode mode,
+                         bool* ok, uint8_t* stage, uint8_t* dstage);
+  // kPipeline
   Status run_host(const Matrix& rows, const std::vector<cfsec_shard*>& ins,
                   const std::vector<cfsec_shard*>& outs, size_t S, MatVecMode mode, bool* ok);
+  // kStagedWhole: whole rows through the workspace, for the Verify of more inputs than one launch carries
+  Status run_staged_verify(const Matrix& rows, const std::vector<cfsec_shard*>& all, size_t S, bool* ok);
   // encode_stripes (nstore = m) and verify_stripes (nstore = 0): the parity rows over whole stripes
   Status whole_stripes(cfsec_shard* const* stripes, int nst, int mem, int* status, int nstore);
   RSEngine() = default;
@@ -403,6 +480,20 @@ class RSEngine {
   Status run_device(std::vector<StripeTask*>& tasks, int mem, DeviceContext* ctx, const AsyncOut* async,
                     const CrcOut* crc);
 };
+
+// The way a single-stripe call (RSEngine::run) takes, from facts gathered before anything is queued:
+//   kInPlace        device memory: the rows as they are, on the caller's stream
+//   kPinnedInPlace  host memory, every row page-locked (rows_aliasable: device_alias took every input
+//                   and output row): the kernel reads and writes them over PCIe, no copies
+//   kSmallStage     other host calls moving at most kSmallPageable bytes, with a page-locked stage
+//                   the GPU addresses (stage_usable): copied there on the CPU and coded in place
+//   kPipeline       other host calls: run_host's chunked two-stream pipeline
+//   kStagedWhole    host Verify of more inputs than one launch carries (mode == kVerify && nin > 32)
+//                   whose rows are not all page-locked: whole rows staged, two launches
+// Host arithmetic only; tests/test_call_path.py pins the table.
+enum class CallPath { kInPlace, kPinnedInPlace, kSmallStage, kPipeline, kStagedWhole };
+CallPath single_call_path(bool host, bool rows_aliasable, bool stage_usable, size_t moved_bytes, int nin,
+                          MatVecMode mode);
 
 // Counting semaphore (util/limit/count.NewBlockingCount, encoder.go:90).
 class BlockingCount {

@@ -182,3 +182,24 @@ def test_encode_crc_single_call(rs, memory, k, m, S):
     for i in range(k + m):
         assert np.array_equal(got[i], want[i]), i
         assert words[i] == crc(want[i]), i
+
+
+@pytest.mark.parametrize("pinned_rows", [range(0, 6), range(6, 12)], ids=["data_pinned", "parity_pinned"])
+@pytest.mark.parametrize("delta", [-1, 1])
+def test_encode_crc_mixed_pinned_and_pageable_rows(rs, pinned_rows, delta):
+    """cfsec_rs_encode_crc over a stripe whose rows are part page-locked, part pageable (EC6P6, at both
+    sides of the single-stripe calls' 1 MiB boundary): one pageable row and every row is staged whole.
+    Parity bytes equal the oracle's, all 12 words zlib's."""
+    from chubaofs_amd import _lib
+    k, m = 6, 6
+    S = (1 << 20) // (k + m) + delta
+    r = np.random.default_rng(S + pinned_rows[0])
+    sh = [_lib.pinned_empty(S) if i in pinned_rows else np.zeros(S, np.uint8) for i in range(k + m)]
+    for i in range(k + m):
+        sh[i][:] = r.integers(0, 256, S, dtype=np.uint8) if i < k else 0
+    want = [s.copy() for s in sh]
+    assert O.encode(k, m, want) == 0
+    words = rs.New(k, m).EncodeCRC(sh)
+    for i in range(k + m):
+        assert np.array_equal(sh[i], want[i]), i
+        assert words[i] == crc(want[i]), i

@@ -105,3 +105,107 @@ def test_small_pageable_staging_boundary(k, m, delta):
     enc.Reconstruct(work)
     for i in range(k + m):
         assert np.array_equal(work[i], want[i]), i
+
+
+def make_mixed(k, m, S, pinned_rows, seed):
+    """Separate buffers per shard: page-locked for the shard indices in pinned_rows, pageable for the rest."""
+    r = np.random.default_rng(seed)
+    out = []
+    for i in range(k + m):
+        a = alloc(S, i in pinned_rows)
+        a[:] = r.integers(0, 256, S, dtype=np.uint8) if i < k else 0
+        out.append(a)
+    return out
+
+
+@pytest.fixture(scope="module")
+def wide_codewords():
+    """The oracle's 40 + 3 codewords, computed once per size and never changed."""
+    k, m, out = 40, 3, {}
+    for S in (1000, 4097):
+        r = np.random.default_rng(S)
+        want = [r.integers(0, 256, S, dtype=np.uint8) for _ in range(k)] + [np.zeros(S, np.uint8) for _ in range(m)]
+        assert O.encode(k, m, want) == 0
+        for w in want:
+            w.setflags(write=False)
+        out[S] = want
+    return out
+
+
+@pytest.mark.parametrize("pinned", [False, True], ids=["pageable", "pinned"])
+@pytest.mark.parametrize("S", [1000, 4097])
+def test_wide_host_verify_and_encode(wide_codewords, pinned, S):
+    """k = 40: Verify of more inputs than one launch carries, two launches (store into staging, compare).
+    Page-locked rows are coded in place (kPinnedInPlace); pageable rows go whole through the workspace
+    (kStagedWhole), the one way through RSEngine::run that only this test takes.  Encode of the same
+    rows (one launch) takes the small stage or runs in place."""
+    k, m = 40, 3
+    want = wide_codewords[S]
+    sh = [alloc(S, pinned) for _ in range(k + m)]
+    for i in range(k):
+        sh[i][:] = want[i]
+    for i in range(k, k + m):
+        sh[i][:] = 0
+    enc = rs().New(k, m)
+    enc.Encode(sh)
+    for i in range(k + m):
+        assert np.array_equal(sh[i], want[i]), i
+    assert enc.Verify(sh)
+    sh[k + m - 1][S - 1] ^= 1
+    assert not enc.Verify(sh)
+    sh[k + m - 1][S - 1] ^= 1
+    sh[39][S // 3] ^= 0x40
+    assert not enc.Verify(sh)
+    assert O.verify(k, m, [s.copy() for s in sh]) == (0, False)
+    sh[39][S // 3] ^= 0x40
+    assert enc.Verify(sh)
+    assert O.verify(k, m, [s.copy() for s in sh]) == (0, True)
+
+
+@pytest.mark.parametrize("pinned_rows", [range(0, 6), range(6, 12)], ids=["data_pinned", "parity_pinned"])
+@pytest.mark.parametrize("delta", [-1, 1], ids=["small_stage", "pipeline"])
+def test_mixed_pinned_and_pageable_rows(pinned_rows, delta):
+    """A stripe whose rows are part page-locked, part pageable is not coded in place: one pageable row
+    sends the call to the small stage (at most 1 MiB moved) or the pipeline (more).  EC6P6 at both
+    sides of that boundary: Encode, Verify (clean, one flipped byte caught), Reconstruct of {1, 6};
+    every shard's bytes equal the oracle's."""
+    k, m = 6, 6
+    S = (1 << 20) // (k + m) + delta
+    sh = make_mixed(k, m, S, pinned_rows, seed=S + pinned_rows[0])
+    want = [s.copy() for s in sh]
+    assert O.encode(k, m, want) == 0
+    enc = rs().New(k, m)
+    enc.Encode(sh)
+    for i in range(k + m):
+        assert np.array_equal(sh[i], want[i]), i
+    assert enc.Verify(sh)
+    for i, pos in ((2, S - 1), (k + 1, S // 2)):  # a data row, a parity row: one of each kind of memory
+        sh[i][pos] ^= 0x04
+        assert not enc.Verify(sh), i
+        sh[i][pos] ^= 0x04
+    assert enc.Verify(sh)
+    work = [s[:0] if i in (1, 6) else s for i, s in enumerate(sh)]
+    enc.Reconstruct(work)
+    assert all(len(w) == S for w in work)
+    for i in range(k + m):
+        assert np.array_equal(work[i], want[i]), i
+    # the surviving rows were inputs only: unchanged
+    for i in range(k + m):
+        assert np.array_equal(sh[i], want[i]), i
+
+
+@pytest.mark.parametrize("delta", [-1, 1], ids=["small", "pipeline_size"])
+def test_no_parity_rows_host_encode_and_verify(delta):
+    """New(k, 0): a call with no output rows is done before any path is chosen.  Pageable rows at both
+    sides of the 1 MiB boundary: Encode returns and leaves the data as it was, Verify is true."""
+    k = 6
+    S = (1 << 20) // k + delta
+    r = np.random.default_rng(S)
+    sh = [r.integers(0, 256, S, dtype=np.uint8) for _ in range(k)]
+    want = [s.copy() for s in sh]
+    assert O.encode(k, 0, want) == 0 and O.verify(k, 0, want) == (0, True)
+    enc = rs().New(k, 0)
+    enc.Encode(sh)
+    assert enc.Verify(sh)
+    for i in range(k):
+        assert np.array_equal(sh[i], want[i]), i

@@ -3,8 +3,11 @@
 // Python: cfsec_ec_reconstruct_data on HBM shards, median over repeated calls, beside the floor a
 // synchronous call cannot go under (one trivial kernel launched and waited for, by
 // hipStreamSynchronize and by a polled marker word); round 6: the same segments in page-locked and in
-// pageable host memory with a NULL stream (the Go shim's CFSEC_MEM_HOST call).  Build: make -C tools seg_latency (links
-// ../chubaofs_amd/libcfsec.so).  CFSEC_HOST_TIMING=1 adds the engine's phase times on stderr.
+// pageable host memory with a NULL stream (the Go shim's CFSEC_MEM_HOST call).  Build, from the
+// repository root (links chubaofs_amd/libcfsec.so):
+//   hipcc --offload-arch=gfx950 -O3 -std=c++17 tools/seg_latency.hip -o tools/seg_latency
+//         -Lchubaofs_amd -lcfsec -Wl,-rpath,'$ORIGIN/../chubaofs_amd'     (one command line)
+// CFSEC_HOST_TIMING=1 adds the engine's phase times on stderr.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
