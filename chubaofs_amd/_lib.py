@@ -104,6 +104,7 @@ SIGNATURES = {
     "cfsec_rs_encode_stripes": ([_V, P_SHARD, _I, _I, _V], _I),
     "cfsec_rs_verify_stripes": ([_V, P_SHARD, _I, _I, _V], _I),
     "cfsec_rs_reconstruct_stripes": ([_V, P_SHARD, _I, _I, _I, _V], _I),
+    "cfsec_rs_reconstruct_data_stripes": ([_V, P_SHARD, _I, _I, _V], _I),
     "cfsec_codemode_tactic": ([_I, _P(TacticC)], _I),
     "cfsec_ec_new": ([_P(TacticC), _I, _I, _I, _P(_V)], _I),
     "cfsec_ec_free": ([_V], None),
@@ -117,6 +118,7 @@ SIGNATURES = {
     "cfsec_ec_set_devices": ([_V, _V, _I], _I),
     "cfsec_ec_encode_batch": ([_V, P_SHARD, _I, _I, _I, _V], _I),
     "cfsec_ec_reconstruct_batch": ([_V, P_SHARD, _I, _I, _V, _V, _I, _I, _V], _I),
+    "cfsec_ec_reconstruct_data_batch": ([_V, P_SHARD, _I, _I, _V, _V, _I, _V], _I),
     "cfsec_ec_reconstruct_batch_async": ([_V, P_SHARD, _I, _I, _V, _V, _I, _V, _V, _V, _V], _I),
     "cfsec_ec_encode_batch_async": ([_V, P_SHARD, _I, _I, _V, _V, _V, _V], _I),
     "cfsec_ec_encode_batch_crc": ([_V, P_SHARD, _I, _I, _I, _V, _V], _I),

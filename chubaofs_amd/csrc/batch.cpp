@@ -16,6 +16,7 @@
 #include <thread>
 
 #include "engine.hpp"
+#include "gf_mix.hpp"
 
 namespace cfsec {
 namespace {
@@ -353,6 +354,79 @@ size_t pack_chunk(const StripeTask* const* tasks, size_t n, size_t i0, size_t la
   return i1;
 }
 
+MixPack pack_mix(const StripeTask* const* tasks, uint8_t* const* const* rows, size_t n, size_t max_len, uint8_t* dst,
+                 size_t cap) {
+  MixPack pk;
+  // the sizing pass: which tasks go in, their tiles and rows, one coefficient block per plan
+  std::map<const StripePlan*, uint32_t> coef_at;  // plan -> byte offset within the coefficient area
+  std::vector<size_t> take;
+  size_t nrows = 0, ncoef = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const StripeTask& t = *tasks[i];
+    const StripePlan& p = *t.plan;
+    const size_t k = p.in.size(), m = p.out.size();
+    const uint64_t tiles = ((uint64_t)t.len + kMixTile - 1) / kMixTile;
+    const bool ok = !p.compares() && !p.dy16 && m > 0 && k > 0 && k <= (size_t)kLaunchMaxRows && t.len > 0 &&
+                    t.len <= max_len && !t.crc && tiles <= kMixMaxTiles - pk.tiles;
+    if (!ok) {
+      pk.left.push_back(i);
+      continue;
+    }
+    take.push_back(i);
+    pk.tiles += (uint32_t)tiles;
+    nrows += k + m;
+    if (coef_at.emplace(&p, (uint32_t)ncoef).second) ncoef += align_up(k * m, 16);
+  }
+  pk.items = (uint32_t)take.size();
+  pk.plans = (uint32_t)coef_at.size();
+  MixHead h{};
+  h.nitems = pk.items;
+  h.ntiles = pk.tiles;
+  h.nplans = pk.plans;
+  h.items_off = (uint32_t)sizeof(MixHead);
+  h.rows_off = h.items_off + pk.items * (uint32_t)sizeof(MixItem);
+  const size_t map_off = h.rows_off + nrows * 8;
+  const size_t coef_off = align_up(map_off + (size_t)pk.tiles * 4, 16);
+  pk.bytes = coef_off + ncoef;
+  if (pk.bytes > 0xFFFFFFFFu) {  // 32-bit offsets: never with kMixMaxTiles tiles of rows a launch addresses
+    pk = MixPack();
+    for (size_t i = 0; i < n; ++i) pk.left.push_back(i);
+    return pk;
+  }
+  h.map_off = (uint32_t)map_off;
+  h.coef_off = (uint32_t)coef_off;
+  h.bytes = (uint32_t)pk.bytes;
+  if (!dst || cap < pk.bytes || pk.items == 0) return pk;
+  std::memcpy(dst, &h, sizeof h);
+  MixItem* item = reinterpret_cast<MixItem*>(dst + h.items_off);
+  uint64_t* row = reinterpret_cast<uint64_t*>(dst + h.rows_off);
+  uint32_t* tile_item = reinterpret_cast<uint32_t*>(dst + h.map_off);
+  uint32_t tile = 0, at = 0;
+  for (size_t j = 0; j < take.size(); ++j) {
+    const StripeTask& t = *tasks[take[j]];
+    const StripePlan& p = *t.plan;
+    const uint32_t k = (uint32_t)p.in.size(), m = (uint32_t)p.out.size();
+    MixItem& it = item[j];
+    it.len = t.len;
+    it.k = k;
+    it.m = m;
+    it.coef = h.coef_off + coef_at[&p];
+    it.rows = at;
+    it.tile0 = tile;
+    it.ntiles = (uint32_t)((t.len + kMixTile - 1) / kMixTile);
+    for (uint32_t r = 0; r < k + m; ++r) row[at++] = (uint64_t)(uintptr_t)rows[take[j]][r];
+    for (uint32_t q = 0; q < it.ntiles; ++q) tile_item[tile++] = (uint32_t)j;
+  }
+  std::memset(dst + map_off + (size_t)pk.tiles * 4, 0, coef_off - (map_off + (size_t)pk.tiles * 4));
+  for (const auto& kv : coef_at) {
+    const size_t sz = kv.first->in.size() * kv.first->out.size();
+    uint8_t* c = dst + h.coef_off + kv.second;
+    std::memcpy(c, kv.first->rows.v.data(), sz);
+    std::memset(c + sz, 0, align_up(sz, 16) - sz);
+  }
+  return pk;
+}
+
 void partition_stripes(const uint64_t* bytes, int n, int ndev, int* dev) {
   // Stripe i goes to the device whose share of the byte total holds the midpoint of stripe i's
   // bytes: contiguous, non-decreasing runs whose loads differ by at most one stripe's bytes.
@@ -389,7 +463,7 @@ Status RSEngine::set_devices(const int* devices, int n) {
 }
 
 Status RSEngine::plan_stripe(const std::vector<bool>& present, bool verify, StripePlan* plan,
-                             const ExtraRows* extra) {
+                             const ExtraRows* extra, bool data_only) {
   // KRS/reedsolomon.go:1453-1501: the first k present rows in index order, decode matrix from the
   // inversion cache (key: the invalid rows met before the k-th valid one).
   std::vector<int> invalid;
@@ -416,8 +490,9 @@ Status RSEngine::plan_stripe(const std::vector<bool>& present, bool verify, Stri
   plan->out.clear();
   for (int i = 0; i < k_; ++i)
     if (!present[i]) plan->out.push_back(i);
-  for (int i = k_; i < total(); ++i)
-    if (!present[i]) plan->out.push_back(i);
+  if (!data_only)  // ReconstructData leaves the missing parity missing (:1434, 1526-1528)
+    for (int i = k_; i < total(); ++i)
+      if (!present[i]) plan->out.push_back(i);
   plan->nstore = (int)plan->out.size();
   if (verify)
     for (int i = k_; i < total(); ++i)
@@ -442,7 +517,8 @@ Status RSEngine::plan_stripe(const std::vector<bool>& present, bool verify, Stri
       }
     }
   }
-  plan_dy16(present, dec, plan, plan->nextra ? extra : nullptr);
+  plan->dy16.reset();
+  if (!data_only) plan_dy16(present, dec, plan, plan->nextra ? extra : nullptr);
   return CFSEC_OK;
 }
 
@@ -573,9 +649,18 @@ Status RSEngine::reconstruct_stripes(cfsec_shard* const* stripes, int nst, int m
   return run_stripes(tasks, mem);
 }
 
+Status RSEngine::reconstruct_data_stripes(cfsec_shard* const* stripes, int nst, int mem, int* status) {
+  if (nst < 0 || (nst > 0 && (!stripes || !status))) return CFSEC_ERR_INVALID_ARG;
+  PlanStore store;
+  std::vector<StripeTask> tasks;
+  plan_reconstruct_tasks(stripes, nst, false, status, 0, 0, &store, &tasks, nullptr, nullptr, /*data_only=*/true);
+  return run_stripes(tasks, mem, nullptr, nullptr, /*mix=*/true);
+}
+
 void RSEngine::plan_reconstruct_tasks(cfsec_shard* const* stripes, int nst, bool verify, int* status, int phase,
                                       int owner0, PlanStore* store, std::vector<StripeTask>* tasks,
-                                      const ExtraRows* extra, const std::vector<bool>* fuse) {
+                                      const ExtraRows* extra, const std::vector<bool>* fuse, bool data_only) {
+  if (verify) data_only = false;
   StripePlan* vplan = nullptr;  // Verify as an encode-matrix pass (split_verify)
   std::map<const StripePlan*, StripePlan*> store_only;
   tasks->reserve(tasks->size() + (size_t)nst);
@@ -591,10 +676,11 @@ void RSEngine::plan_reconstruct_tasks(cfsec_shard* const* stripes, int nst, bool
       status[s] = st;
       continue;
     }
-    int np = 0;
+    int np = 0, dp = 0;
     for (int i = 0; i < total(); ++i) {
       present[i] = sh[i].len != 0;
       np += present[i] ? 1 : 0;
+      dp += present[i] && i < k_ ? 1 : 0;
     }
     if (np < k_) {
       status[s] = CFSEC_ERR_TOO_FEW_SHARDS;
@@ -602,11 +688,12 @@ void RSEngine::plan_reconstruct_tasks(cfsec_shard* const* stripes, int nst, bool
     }
     const bool fx = verify && extra && fuse && (*fuse)[s];
     if (np == total() && (!verify || (m_ == 0 && !fx))) continue;  // Reconstruct of a full stripe is a no-op
+    if (data_only && dp == k_) continue;  // no data shard missing (KRS/reedsolomon.go:1434)
     // plans are keyed by the present shards, plus whether the extra rows ride along
     present.push_back(fx);
     if (!last_plan || present != last_present) {
       present.pop_back();
-      last_plan = cached_plan(present, fx, verify, fx ? extra : nullptr, store, &st);
+      last_plan = cached_plan(present, fx, verify, fx ? extra : nullptr, store, &st, data_only);
       present.push_back(fx);
       last_present = present;
       if (!last_plan) {
@@ -656,17 +743,18 @@ void RSEngine::plan_reconstruct_tasks(cfsec_shard* const* stripes, int nst, bool
 }
 
 const StripePlan* RSEngine::cached_plan(const std::vector<bool>& present, bool fx, bool verify,
-                                        const ExtraRows* extra, PlanStore* store, Status* st) {
+                                        const ExtraRows* extra, PlanStore* store, Status* st, bool data_only) {
   std::vector<bool> key = present;
   key.push_back(fx);
   key.push_back(verify);
+  key.push_back(data_only);
   {
     std::lock_guard<std::mutex> l(plan_mu_);
     auto it = plan_cache_.find(key);
     if (it != plan_cache_.end()) return it->second.get();
   }
   std::unique_ptr<StripePlan> p(new StripePlan());
-  *st = plan_stripe(present, verify, p.get(), extra);
+  *st = plan_stripe(present, verify, p.get(), extra, data_only);
   if (*st != CFSEC_OK) return nullptr;
   std::lock_guard<std::mutex> l(plan_mu_);
   auto it = plan_cache_.find(key);  // another caller may have planned it meanwhile
@@ -685,7 +773,8 @@ bool RSEngine::split_verify(const StripePlan& p) const {
   return false;
 }
 
-Status RSEngine::run_stripes(std::vector<StripeTask>& tasks, int mem, const AsyncOut* async, const CrcOut* crc) {
+Status RSEngine::run_stripes(std::vector<StripeTask>& tasks, int mem, const AsyncOut* async, const CrcOut* crc,
+                             bool mix) {
   if (tasks.empty()) return CFSEC_OK;
   if (devs_.empty()) {
     set_last_error("no HIP device available to the cfsec engine");
@@ -749,10 +838,10 @@ Status RSEngine::run_stripes(std::vector<StripeTask>& tasks, int mem, const Asyn
   for (int d = 1; d < nd; ++d)
     if (!per[d].empty())
       threads.emplace_back([&, d] {
-        st[d] = run_device(per[d], mem, devs_[d], nullptr, crc);
+        st[d] = run_device(per[d], mem, devs_[d], nullptr, crc, mix);
         if (st[d] != CFSEC_OK) err[d] = last_error_cstr();
       });
-  if (!per[0].empty()) st[0] = run_device(per[0], mem, devs_[0], async, crc);
+  if (!per[0].empty()) st[0] = run_device(per[0], mem, devs_[0], async, crc, mix && !async);
   for (auto& th : threads) th.join();
   for (int d = 1; d < nd; ++d)
     if (st[d] != CFSEC_OK && st[0] == CFSEC_OK) {
@@ -763,6 +852,13 @@ Status RSEngine::run_stripes(std::vector<StripeTask>& tasks, int mem, const Asyn
 }
 
 namespace {
+
+// The length limit of the mixed launch for this call: kMixMaxLen, or CFSEC_MIX_MAX_LEN (read per call,
+// so tests force either route; 0 switches the mixed launch off).
+size_t mix_max_len() {
+  const char* v = std::getenv("CFSEC_MIX_MAX_LEN");
+  return v && *v ? (size_t)std::strtoull(v, nullptr, 10) : kMixMaxLen;
+}
 
 // One run_device call: its workspace and lanes, what it found out about the tasks, and the flag and
 // checksum bookkeeping of the parts launched so far.
@@ -793,6 +889,10 @@ struct BatchRun {
   int next_flag = 0;
   std::vector<std::pair<StripeTask*, int>> flags;  // (task, flag word; -1: written directly)
   int chunk = 0;                                   // staged chunks so far: chunk c runs on lane c % nlanes
+  // the mixed-plan launch (ReconstructData batches): tasks of at most mix_len bytes share one launch
+  // per part (launch_mixed); 0: every task goes through the launch groups
+  DeviceContext* ctx = nullptr;
+  size_t mix_len = 0;
 
   Status join(int from, int to) { return lane_wait(ws->ev, lane[from], lane[to]); }
   void classify(const std::vector<StripeTask*>& tasks, int mem);
@@ -802,6 +902,7 @@ struct BatchRun {
   Status run_phase(int ph);
   Status run_staged(const std::vector<StripeTask*>& sph);
   Status launch_part(const Part& part, hipStream_t s, bool fuse_crc);
+  Status launch_mixed(const Part& part, hipStream_t s, Part* rest, bool* split);
   Status checksum(const Part& part, const std::vector<char>& taken, hipStream_t s);
   Status gather(Status st);
   void hand_back(const std::vector<StripeTask*>& tasks);
@@ -849,6 +950,7 @@ Status BatchRun::acquire(DeviceContext* ctx, size_t ntasks) {
   const Status st = ctx->acquire(lane_bytes * nlanes, std::max(ntasks, (size_t)nitems), &ws, ntasks,
                                  sums && !async ? crc->n : 0);
   if (st != CFSEC_OK) return st;
+  ws->mix_busy[0] = ws->mix_busy[1] = false;  // the workspace's previous call has finished its lanes
   dcrc = !sums ? nullptr : async ? crc->words : ws->dcrc;
   lane[0] = async ? async->stream : ws->stream;
   lane[1] = ws->stream2;
@@ -953,8 +1055,15 @@ Status BatchRun::run_staged(const std::vector<StripeTask*>& sph) {
 // addresses the product used; staged rows before their lane is reused).
 // fuse_crc: try the launches that checksum within the product's own pass (fused_crc_group) and, for
 // the call's first launch, the dy16 repair that zeroes the words itself (zero_first).  On for the in-place part, off for staged chunks, whose rows take the separate pass.
-Status BatchRun::launch_part(const Part& part, hipStream_t s, bool fuse_crc) {
+Status BatchRun::launch_part(const Part& whole, hipStream_t s, bool fuse_crc) {
   Status st = CFSEC_OK;
+  // ReconstructData batches: the small store-only tasks, two or more, as one mixed launch whatever
+  // their plans; the rest (a lone small task too: the fixed-K kernels do that better) in groups
+  Part rest;
+  bool split = false;
+  if (mix_len) st = launch_mixed(whole, s, &rest, &split);
+  if (st != CFSEC_OK) return st;
+  const Part& part = split ? rest : whole;
   std::vector<Group> groups;
   {
     HostTimer gt("      make_groups");
@@ -993,6 +1102,40 @@ Status BatchRun::launch_part(const Part& part, hipStream_t s, bool fuse_crc) {
   for (const Group& gr : groups)
     for (size_t i = 0; i < gr.tasks.size(); ++i) flags.emplace_back(gr.tasks[i], gr.direct ? -1 : gr.flag0 + (int)i);
   if (st == CFSEC_OK) st = checksum(part, taken, s);
+  return st;
+}
+
+// The tasks of a part the item table takes (pack_mix), when there are at least two, as one mixed
+// launch on stream s: the table packed into the lane's page-locked buffer, one copy to the device,
+// the launch.  *rest gets the other tasks (*split true); with fewer than two takers nothing is
+// launched and *split stays false.
+Status BatchRun::launch_mixed(const Part& part, hipStream_t s, Part* rest, bool* split) {
+  HostTimer mt("      launch_mixed");
+  const size_t n = part.tasks.size();
+  const MixPack sz = pack_mix(part.tasks.data(), part.rows.data(), n, mix_len, nullptr, 0);
+  if (sz.items < 2) return CFSEC_OK;
+  const int slot = nlanes > 1 && s == lane[1] ? 1 : 0;
+  Status st = ctx->reserve_mix(ws, slot, sz.bytes, s);
+  if (st != CFSEC_OK) return st;
+  if (ws->mix_busy[slot]) {  // the lane's previous table is still being copied from
+    st = hip_status(hipEventSynchronize(ws->mix_ev[slot]), "hipEventSynchronize(mix table)");
+    ws->mix_busy[slot] = false;
+    if (st != CFSEC_OK) return st;
+  }
+  const MixPack pk = pack_mix(part.tasks.data(), part.rows.data(), n, mix_len, ws->hmix[slot], ws->mix_cap[slot]);
+  st = hip_status(hipMemcpyAsync(ws->dmix[slot], ws->hmix[slot], pk.bytes, hipMemcpyHostToDevice, s),
+                  "hipMemcpyAsync H2D(mix table)");
+  if (st == CFSEC_OK) st = hip_status(hipEventRecord(ws->mix_ev[slot], s), "hipEventRecord(mix table)");
+  ws->mix_busy[slot] = true;
+  if (st == CFSEC_OK) st = hip_status(launch_mix(ws->dmix[slot], pk.tiles, s), "launch_mix");
+  const char* tr = std::getenv("CFSEC_TRACE_MATVEC");
+  if (tr && tr[0] && tr[0] != '0')
+    std::fprintf(stderr, "cfsec: mix items=%u tiles=%u plans=%u\n", pk.items, pk.tiles, pk.plans);
+  for (size_t i : pk.left) {
+    rest->tasks.push_back(part.tasks[i]);
+    rest->rows.push_back(part.rows[i]);
+  }
+  *split = true;
   return st;
 }
 
@@ -1058,12 +1201,14 @@ void BatchRun::hand_back(const std::vector<StripeTask*>& tasks) {
 // A batch call on one device: classify the tasks, size the lanes, acquire and zero, run the phases
 // (each: the in-place part, then the staged chunks), gather the flags, sync, hand back the results.
 Status RSEngine::run_device(std::vector<StripeTask*>& tasks, int mem, DeviceContext* ctx, const AsyncOut* async,
-                            const CrcOut* crc) {
+                            const CrcOut* crc, bool mix) {
   HostTimer whole("  run_device");
   std::unique_ptr<HostTimer> tm(new HostTimer("    classify + acquire"));
   DeviceGuard g(ctx->device());
   if (!g.ok()) return hip_status(hipErrorInvalidDevice, "hipSetDevice");
   BatchRun run{async, crc};
+  run.ctx = ctx;
+  run.mix_len = mix ? mix_max_len() : 0;
   run.classify(tasks, mem);
   if (async && (!run.staged.empty() || (run.checks && !async->flags))) return CFSEC_ERR_INVALID_ARG;
   run.size_lanes();
@@ -1326,6 +1471,57 @@ Status LrcEncoder::reconstruct_batch(cfsec_shard* shards, int n, int nbids, cons
     status[pos[i]] = s;
   }
   clear_failed_crcs(crc, async, status, nbids, n);
+  return rc;
+}
+
+Status ECEncoder::reconstruct_data_batch(cfsec_shard* shards, int n, int nitems, const int* bad, const int* bad_off,
+                                         int mem, int* status) {
+  // encoder.go:146-151 per item (initBadShards, engine ReconstructData), in reconstruct_data's order
+  if (!shards || !status || !bad_off || nitems < 0) return CFSEC_ERR_INVALID_ARG;
+  Slot slot(pool_.get());
+  std::vector<cfsec_shard*> stripes;
+  std::vector<int> pos;
+  for (int b = 0; b < nitems; ++b) {
+    cfsec_shard* sh = shards + (size_t)b * n;
+    status[b] = init_bad_shards(sh, n, std::vector<int>(bad + bad_off[b], bad + bad_off[b + 1]));
+    if (status[b] == CFSEC_OK && n != engine_->total()) status[b] = CFSEC_ERR_TOO_FEW_SHARDS;  // reedsolomon.go:1408-1410
+    if (status[b] != CFSEC_OK) continue;
+    stripes.push_back(sh);
+    pos.push_back(b);
+  }
+  std::vector<int> st(stripes.size());
+  const Status rc = engine_->reconstruct_data_stripes(stripes.data(), (int)stripes.size(), mem, st.data());
+  for (size_t i = 0; i < pos.size(); ++i) status[pos[i]] = st[i];
+  return rc;
+}
+
+Status LrcEncoder::reconstruct_data_batch(cfsec_shard* shards, int n, int nitems, const int* bad, const int* bad_off,
+                                          int mem, int* status) {
+  // lrcencoder.go:188-201 per item: fillFullShards over the global stripe, the global bad indices
+  // only, the global engine's ReconstructData over shards [0, N+M)
+  if (!shards || !status || !bad_off || nitems < 0) return CFSEC_ERR_INVALID_ARG;
+  const int N = t_.n, M = t_.m;
+  Slot slot(pool_.get());
+  std::vector<cfsec_shard*> stripes;
+  std::vector<int> pos;
+  for (int b = 0; b < nitems; ++b) {
+    cfsec_shard* sh = shards + (size_t)b * n;
+    if (n < N + M) {
+      status[b] = CFSEC_ERR_INVALID_SHARDS;
+      continue;
+    }
+    status[b] = fill_full_shards(sh, N + M);
+    std::vector<int> global_bad;
+    for (int i = bad_off[b]; i < bad_off[b + 1]; ++i)
+      if (bad[i] < N + M) global_bad.push_back(bad[i]);
+    if (status[b] == CFSEC_OK) status[b] = init_bad_shards(sh, n, global_bad);
+    if (status[b] != CFSEC_OK) continue;
+    stripes.push_back(sh);
+    pos.push_back(b);
+  }
+  std::vector<int> st(stripes.size());
+  const Status rc = engine_->reconstruct_data_stripes(stripes.data(), (int)stripes.size(), mem, st.data());
+  for (size_t i = 0; i < pos.size(); ++i) status[pos[i]] = st[i];
   return rc;
 }
 

@@ -396,6 +396,15 @@ int cfsec_rs_reconstruct_stripes(cfsec_rs* h, cfsec_shard* shards, int nstripes,
   });
 }
 
+int cfsec_rs_reconstruct_data_stripes(cfsec_rs* h, cfsec_shard* shards, int nstripes, int mem, int* status) {
+  if (!h || nstripes < 0 || (nstripes > 0 && (!shards || !status))) return CFSEC_ERR_INVALID_ARG;
+  if (nstripes == 0) return CFSEC_OK;
+  return guarded([&] {
+    auto v = stripe_views(shards, nstripes, h->e->total());
+    return h->e->reconstruct_data_stripes(v.data(), nstripes, mem, status);
+  });
+}
+
 // ---------------- ec.Encoder ----------------
 
 int cfsec_codemode_tactic(int codemode, cfsec_tactic* t) {
@@ -463,6 +472,14 @@ int cfsec_ec_reconstruct_batch(cfsec_ec* h, cfsec_shard* shards, int n, int nbid
   if (!h || nbids < 0 || n <= 0 || (nbids > 0 && (!shards || !status || !bad_off))) return CFSEC_ERR_INVALID_ARG;
   if (!bad_off_valid(nbids, bad_off, bad_idx)) return CFSEC_ERR_INVALID_ARG;
   return guarded([&] { return h->e->reconstruct_batch(shards, n, nbids, bad_idx, bad_off, mem, verify != 0, status); });
+}
+
+int cfsec_ec_reconstruct_data_batch(cfsec_ec* h, cfsec_shard* shards, int n, int nitems, const int* bad_idx,
+                                    const int* bad_off, int mem, int* status) {
+  if (!h || nitems < 0) return CFSEC_ERR_INVALID_ARG;
+  if (nitems == 0) return CFSEC_OK;
+  if (n <= 0 || !shards || !status || !bad_off || !bad_off_valid(nitems, bad_off, bad_idx)) return CFSEC_ERR_INVALID_ARG;
+  return guarded([&] { return h->e->reconstruct_data_batch(shards, n, nitems, bad_idx, bad_off, mem, status); });
 }
 
 int cfsec_ec_encode_batch(cfsec_ec* h, cfsec_shard* shards, int n, int nstripes, int mem, int* status) {

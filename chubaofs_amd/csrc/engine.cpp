@@ -273,6 +273,28 @@ void DeviceContext::release(Workspace* ws) {
   free_.push_back(ws);
 }
 
+Status DeviceContext::reserve_mix(Workspace* ws, int slot, size_t bytes, hipStream_t stream) {
+  Status st = CFSEC_OK;
+  if (!ws->mix_ev[slot])
+    st = hip_status(hipEventCreateWithFlags(&ws->mix_ev[slot], hipEventDisableTiming), "hipEventCreate");
+  if (st != CFSEC_OK || ws->mix_cap[slot] >= bytes) return st;
+  if (ws->mix_busy[slot]) {  // the lane's earlier copy and launch still use the tables
+    st = hip_status(hipStreamSynchronize(stream), "hipStreamSynchronize(mix table)");
+    ws->mix_busy[slot] = false;
+    if (st != CFSEC_OK) return st;
+  }
+  const size_t cap = std::max(align_up(bytes, 4096), size_t(64) << 10);
+  if (ws->hmix[slot]) (void)hipHostFree(ws->hmix[slot]);
+  if (ws->dmix[slot]) (void)hipFree(ws->dmix[slot]);
+  ws->hmix[slot] = ws->dmix[slot] = nullptr;
+  ws->mix_cap[slot] = 0;
+  st = hip_status(hipHostMalloc(reinterpret_cast<void**>(&ws->hmix[slot]), cap, hipHostMallocDefault),
+                  "hipHostMalloc(mix table)");
+  if (st == CFSEC_OK) st = hip_status(hipMalloc(reinterpret_cast<void**>(&ws->dmix[slot]), cap), "hipMalloc(mix table)");
+  if (st == CFSEC_OK) ws->mix_cap[slot] = cap;
+  return st;
+}
+
 // CFSEC_SYNC_POLL=0 (or cfsec_set_sync_poll(0)): hipStreamSynchronize always (A/B, tests)
 std::atomic<int>& sync_poll_mode() {
   static std::atomic<int> mode{[] {

@@ -109,6 +109,14 @@ class DeviceContext {
     uint32_t* hmark = nullptr;
     uint32_t* dmark = nullptr;
     uint32_t seq = 0;
+    // mixed-plan launches (batch.cpp launch_mixed): per lane an item table packed in page-locked host
+    // memory and its device copy; mix_ev follows the copy to the device, so the host table is
+    // repacked only once the previous copy has read it
+    uint8_t* hmix[2] = {nullptr, nullptr};
+    uint8_t* dmix[2] = {nullptr, nullptr};
+    size_t mix_cap[2] = {0, 0};
+    hipEvent_t mix_ev[2] = {nullptr, nullptr};
+    bool mix_busy[2] = {false, false};
   };
   // Wait for everything queued on `stream` so far (a synchronous call's end): the stream writes a
   // sequence number into ws's pinned marker word after its work (hipStreamWriteValue32) and the
@@ -129,6 +137,9 @@ class DeviceContext {
   // host) and `nbflags` batch flag words (zero on return).
   Status acquire(size_t bytes, size_t nflags, Workspace** out, size_t nbflags = 0, size_t ncrc = 0);
   void release(Workspace* ws);
+  // Item-table room of `bytes` (host and device) in lane `slot` of ws; waits for the lane's earlier
+  // table to be done with before it reallocates.
+  Status reserve_mix(Workspace* ws, int slot, size_t bytes, hipStream_t stream);
   // Return a workspace whose work is still queued on `stream`: it is handed out again only once
   // the stream has passed this point.
   void release_after(Workspace* ws, hipStream_t stream);
@@ -337,6 +348,33 @@ std::vector<std::pair<size_t, size_t>> split_runs(const uint8_t* const* in, size
 size_t pack_chunk(const StripeTask* const* tasks, size_t n, size_t i0, size_t lane_bytes,
                   std::vector<size_t>* offsets);
 
+// The item table of a mixed-plan launch (gf_mix.hpp), packed from the tasks that qualify: a store-only
+// plan without a dy16 product, 1 .. kLaunchMaxRows inputs, 0 < len <= max_len, no checksums, and room
+// left below kMixMaxTiles tiles.  rows[i][p] = task i's row p of plan->in followed by plan->out, stored
+// in that order; coefficient rows once per plan (by address).  dst == nullptr, or cap below the bytes
+// needed: nothing is written (the sizing pass).  `left` lists the tasks not packed, in order.  Host
+// arithmetic only (batch.cpp): no device calls, no address is dereferenced.
+struct MixPack {
+  size_t bytes = 0;  // the table's size
+  uint32_t items = 0, tiles = 0, plans = 0;
+  std::vector<size_t> left;
+};
+MixPack pack_mix(const StripeTask* const* tasks, uint8_t* const* const* rows, size_t n, size_t max_len, uint8_t* dst,
+                 size_t cap);
+// Segments up to this length go into a mixed launch (BatchRun::launch_part); CFSEC_MIX_MAX_LEN, read
+// per call, overrides it (0: no mixed launch).  The value is the largest swept length at which the
+// mixed launch was no slower than the launch groups on a one-pattern batch of 64 scattered EC12P4
+// segments in HBM (tools/seg_batch_probe.py --sweep, us per segment, mixed / groups):
+//                 16 KiB        64 KiB        256 KiB       1 MiB
+//   one pattern   0.42 / 0.54   0.52 / 0.65   1.24 / 1.06   3.20 / 2.91
+//   distinct      0.64 / 5.68   0.71 / 6.04   1.39 / 6.11   3.42 / 6.77
+// EC6P6 (6 inputs: the fixed-K kernel's launches are short) does not fit the rule: its one-pattern
+// batch is slower mixed at every swept length (0.38 / 0.32, 0.44 / 0.36, 0.92 / 0.60, 1.97 / 1.58),
+// by 4-5 us per 64-segment call up to 64 KiB -- the table's copy to the device -- while its
+// distinct-pattern batch is faster mixed up to 256 KiB (0.48 / 1.07, 0.52 / 1.12, 1.00 / 1.24,
+// 2.04 / 2.15).  One limit serves both: a batch's patterns are not known to be one until it is planned.
+constexpr size_t kMixMaxLen = size_t(64) << 10;
+
 // Plans built for one batch call (stable addresses for the tasks that point at them).
 struct PlanStore {
   std::vector<std::unique_ptr<StripePlan>> other;
@@ -408,22 +446,30 @@ class RSEngine {
   Status encode_stripes(cfsec_shard* const* stripes, int nst, int mem, int* status);
   Status verify_stripes(cfsec_shard* const* stripes, int nst, int mem, int* status);
   Status reconstruct_stripes(cfsec_shard* const* stripes, int nst, int mem, bool verify, int* status);
+  //   reconstruct_data:    ReconstructData(shards) (KRS/reedsolomon.go:1377-1397): the missing data
+  //                        shards only; small segments of any erasure patterns share one mixed launch
+  Status reconstruct_data_stripes(cfsec_shard* const* stripes, int nst, int mem, int* status);
   // The planning half of reconstruct_stripes: checks every stripe (errors to status[s]), sets the
   // rebuilt shards' lengths and appends the tasks (phase `phase`, and phase + 1 for a split Verify)
   // that run_stripes executes; owner of stripe s = owner0 + s.
   // extra / fuse (optional): stripe s also compares the ExtraRows when fuse[s] (and verify).
+  // data_only (verify false): ReconstructData -- a stripe with every data shard present is a no-op, the
+  // plans hold the missing data shards only, nothing compared, no dy16 product.
   void plan_reconstruct_tasks(cfsec_shard* const* stripes, int nst, bool verify, int* status, int phase,
                               int owner0, PlanStore* store, std::vector<StripeTask>* tasks,
-                              const ExtraRows* extra = nullptr, const std::vector<bool>* fuse = nullptr);
+                              const ExtraRows* extra = nullptr, const std::vector<bool>* fuse = nullptr,
+                              bool data_only = false);
   // Run the tasks' products (device memory, pinned host memory in place, pageable host memory
   // through double-buffered staging), tasks partitioned over the devices.
   // async (device memory, the handle's first device): enqueue on async->stream and return; verify
   // mismatches OR 1 into async->flags[owner] instead of setting the tasks' status.
+  // mix (synchronous calls): small store-only tasks of a part share one mixed-plan launch
+  // (BatchRun::launch_part); false: every task goes through the launch groups.
   Status run_stripes(std::vector<StripeTask>& tasks, int mem, const AsyncOut* async = nullptr,
-                     const CrcOut* crc = nullptr);
-  // Plan of a Reconstruct (+ Verify) over the present shards.
+                     const CrcOut* crc = nullptr, bool mix = false);
+  // Plan of a Reconstruct (+ Verify) over the present shards; data_only: of a ReconstructData.
   Status plan_stripe(const std::vector<bool>& present, bool verify, StripePlan* plan,
-                     const ExtraRows* extra = nullptr);
+                     const ExtraRows* extra = nullptr, bool data_only = false);
   // plan->dy16 where the code and the erasure pattern make that product cheaper (batch.cpp).
   void plan_dy16(const std::vector<bool>& present, const Matrix& dec, StripePlan* plan,
                  const ExtraRows* extra = nullptr) const;
@@ -468,17 +514,17 @@ class RSEngine {
   Matrix parity_;  // m x k (r.parity, KRS/reedsolomon.go:568-571)
   InversionCache tree_;
   // Reconstruct plans across calls (blobnode's tasklets repeat one erasure pattern call after call):
-  // key = the present shards + [extra rows fused] + [verify]; a cached plan is never changed or
+  // key = the present shards + [extra rows fused] + [verify] + [data only]; a cached plan is never changed or
   // freed, so concurrent callers share it.  Beyond kMaxCachedPlans patterns a call keeps its own.
   std::mutex plan_mu_;
   std::map<std::vector<bool>, std::unique_ptr<StripePlan>> plan_cache_;
   static constexpr size_t kMaxCachedPlans = 4096;
   const StripePlan* cached_plan(const std::vector<bool>& present, bool fx, bool verify, const ExtraRows* extra,
-                                PlanStore* store, Status* st);
+                                PlanStore* store, Status* st, bool data_only = false);
   DeviceContext* ctx_ = nullptr;
   std::vector<DeviceContext*> devs_;  // batch devices, ctx_ first
   Status run_device(std::vector<StripeTask*>& tasks, int mem, DeviceContext* ctx, const AsyncOut* async,
-                    const CrcOut* crc);
+                    const CrcOut* crc, bool mix);
 };
 
 // The way a single-stripe call (RSEngine::run) takes, from facts gathered before anything is queued:
@@ -554,6 +600,11 @@ class ECEncoder {
   // crc: every shard's checksum after the Encode into crc->words[s * n + shard].
   virtual Status encode_batch(cfsec_shard* shards, int n, int nstripes, int mem, int* status,
                               const AsyncOut* async = nullptr, const CrcOut* crc = nullptr);
+  // access's degraded reads as one call (stream_get.go:420-431): item i is the n shards at
+  // shards[i*n ..] with bad indices bad[bad_off[i] .. bad_off[i+1]); status[i] = what
+  // reconstruct_data returns for the item alone.  One concurrency slot for the call.
+  virtual Status reconstruct_data_batch(cfsec_shard* shards, int n, int nitems, const int* bad, const int* bad_off,
+                                        int mem, int* status);
 
  protected:
   // Shard index g (< N + M + L) as a row over the N data shards.
@@ -584,6 +635,8 @@ class LrcEncoder : public ECEncoder {
                            const CrcOut* crc = nullptr) override;
   Status encode_batch(cfsec_shard* shards, int n, int nstripes, int mem, int* status,
                       const AsyncOut* async = nullptr, const CrcOut* crc = nullptr) override;
+  Status reconstruct_data_batch(cfsec_shard* shards, int n, int nitems, const int* bad, const int* bad_off, int mem,
+                                int* status) override;
 
  protected:
   bool row_over_data(int g, uint8_t* dst) const override;

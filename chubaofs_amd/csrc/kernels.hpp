@@ -117,6 +117,14 @@ const char* bs_prefix_name(BsPrefix p);          // "none", "encode", "verify", 
 // "cfsec: matvec family=<name> bs=<none|encode|verify|table> mode=.. k=.. m=.. r0=.. c0=.. stripes=..
 // prefix=.. tail=.. affine=..".
 
+// The mixed-plan launch (gf_mix.hip): store-only products of many items, each with its own rows,
+// length, input and output count and coefficient rows, read by the workgroups from the item table at
+// device address `table` (gf_mix.hpp; packed by pack_mix, engine.hpp).  One workgroup per tile of
+// 4 KiB of an item's rows; the argument block holds the table's address and the tile count only, so
+// the item count is unbounded and one launch carries at most kMixMaxTiles tiles.
+constexpr uint32_t kMixMaxTiles = 1u << 24;
+hipError_t launch_mix(const uint8_t* table, uint32_t ntiles, hipStream_t stream);
+
 // launch_dy16_repair's decisions, the same way: per job the table launch, per run the affine
 // bit-sliced prefix and the dyadic tail.
 enum class RepairBs : int { kNone = 0, kAffine, kTable };

@@ -139,6 +139,28 @@ class Encoder:
             return out, [[int(words[b * n + i]) for i in range(n)] for b in range(len(bids))]
         return out
 
+    def ReconstructDataBatch(self, items, badIdx):
+        """access's degraded reads as one call (stream_get.go:420-431): items is a list of shard lists
+        (all of one length n, each item its own segment length), badIdx one index list per item.  Per
+        item exactly ReconstructData(shards, bad): the bad data shards are rebuilt, bad parity stays
+        missing.  Returns the per-item status codes (0 ok, else the code ReconstructData would raise
+        for that item alone)."""
+        if len(items) != len(badIdx):
+            raise ValueError("one bad-index list per item")
+        n = len(items[0]) if items else 0
+        bm = BatchMarshal(items, n, fill=True)
+        flat = [i for b in badIdx for i in b]
+        off = [0]
+        for b in badIdx:
+            off.append(off[-1] + len(b))
+        bad = (ctypes.c_int * max(len(flat), 1))(*flat)
+        offs = (ctypes.c_int * len(off))(*off)
+        status = (ctypes.c_int * max(len(items), 1))()
+        st = self._L.cfsec_ec_reconstruct_data_batch(self._h, bm.arr, n, len(items), bad, offs, bm.mem, status)
+        bm.writeback()
+        _lib.check(st)
+        return [int(status[i]) for i in range(len(items))]
+
     def RepairBatch(self, bids, badIdx, expect=None):
         """blobnode's repair of a tasklet with the checksum work around it (cfsec_ec_repair_batch_crc):
         per bid Reconstruct(shards, bad) then Verify(shards), and crc32.ChecksumIEEE of every shard of

@@ -138,6 +138,12 @@ class ReedSolomon:
         empty) are replaced in the lists by the rebuilt shards.  Per-stripe status codes."""
         return self._stripes(self._L.cfsec_rs_reconstruct_stripes, stripes, True, int(verify))
 
+    def ReconstructDataStripes(self, stripes):
+        """ReconstructData of every stripe in one call: the missing data shards only (missing parity
+        stays missing); small segments of any mix of erasure patterns and lengths share one kernel
+        launch.  Per-stripe status codes, each what ReconstructData would raise for that stripe."""
+        return self._stripes(self._L.cfsec_rs_reconstruct_data_stripes, stripes, True)
+
     # -- helpers / GPU batch API --
     def matrix(self) -> np.ndarray:
         out = np.zeros((self.total_shards, self.data_shards), np.uint8)

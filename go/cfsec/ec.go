@@ -277,6 +277,58 @@ func (e *ECEncoder) reconstructBatch(bids [][][]byte, badIdx [][]int, verify, wa
 	return errs, crcs, toError(st)
 }
 
+// ReconstructDataBatch runs access's degraded reads (stream_get.go:420-431) as one call: for every
+// item, ReconstructData(items[i], badIdx[i]) over segments of the item's own length.  errs[i] is what
+// that call would have reported for the item alone; err reports a failure of the call itself.  The
+// bad data shards are rebuilt into their own buffers (a bad shard keeps its buffer as capacity, as in
+// reconstruct above), bad parity shards come back with len 0.  Worth calling from two or three
+// segments up: the launch and the wait are paid once for the batch (INTEGRATION.md §5a).
+// (Source only, like the rest of this shim: no Go toolchain builds it here.)
+func (e *ECEncoder) ReconstructDataBatch(items [][][]byte, badIdx [][]int) ([]error, error) {
+	if len(items) != len(badIdx) {
+		return nil, errInvalidArg
+	}
+	errs := make([]error, len(items))
+	if len(items) == 0 {
+		return errs, nil
+	}
+	n := len(items[0])
+	N, M := e.tactic.N, e.tactic.M
+	flat := make([][]byte, 0, n*len(items))
+	var bad []C.int
+	off := make([]C.int, 1, len(items)+1)
+	for i, shards := range items {
+		if len(shards) != n {
+			return nil, errInvalidArg
+		}
+		for _, j := range badIdx[i] {
+			// LRC modes name only the global shards bad (lrcencoder.go:192-197)
+			if j >= 0 && j < n && len(shards[j]) != 0 && (e.tactic.L == 0 || j < N+M) {
+				shards[j] = shards[j][:0]
+			}
+			bad = append(bad, C.int(j))
+		}
+		if e.tactic.L == 0 {
+			prepareMissing(shards, N, true)
+		} else if n >= N+M {
+			reserve(shards[:N+M]) // fillFullShards over the global stripe (lrcencoder.go:190)
+		}
+		flat = append(flat, shards...)
+		off = append(off, C.int(len(bad)))
+	}
+	bp := intPtr(bad)
+	status := make([]C.int, len(items))
+	st := callVec(flat, func(v *C.cfsec_shard, _ C.int) C.int {
+		return C.cfsec_ec_reconstruct_data_batch(e.h, v, C.int(n), C.int(len(items)), bp, &off[0],
+			C.CFSEC_MEM_HOST, &status[0])
+	})
+	for i := range items {
+		copy(items[i], flat[i*n:(i+1)*n])
+		errs[i] = ecError(status[i])
+	}
+	return errs, toError(st)
+}
+
 // ErrCrcNotMatch reports a survivor whose checksum is not the one it came with: blobnode's
 // errCrcNotMatch (work_shard_recover.go:654-685, crc1 != crc2).  Use errors.As to learn the shard.
 type ErrCrcNotMatch struct {

@@ -204,6 +204,13 @@ int cfsec_rs_verify_stripes(cfsec_rs* h, cfsec_shard* shards, int nstripes, int 
  * false).  Bit-exact with the two calls on any input, consistent or not. */
 int cfsec_rs_reconstruct_stripes(cfsec_rs* h, cfsec_shard* shards, int nstripes, int verify, int mem,
                                  int* status);
+/* reedsolomon.ReconstructData per stripe (KRS/reedsolomon.go:1377-1397, 1407-1552 with dataOnly):
+ * the missing data shards only (cap >= shard size, len = shard size afterwards); missing parity
+ * shards stay missing, a stripe with no data shard missing is a no-op.  status[s] is what
+ * cfsec_rs_reconstruct_data returns for stripe s alone.  Segments of any mix of erasure patterns,
+ * lengths and byte alignments run as one kernel launch where they are small (the mixed-plan
+ * launch); CFSEC_MIX_MAX_LEN (bytes, read per call; 0: off) overrides the length limit. */
+int cfsec_rs_reconstruct_data_stripes(cfsec_rs* h, cfsec_shard* shards, int nstripes, int mem, int* status);
 
 /* ---------------- ec.Encoder ---------------- */
 /* Code-mode table (codemode.go:26-79): fill *t for a CodeMode value; CFSEC_ERR_INVALID_CODE_MODE
@@ -230,6 +237,16 @@ int cfsec_ec_verify(cfsec_ec* h, cfsec_shard* shards, int n, int mem, void* stre
 int cfsec_ec_reconstruct_batch(cfsec_ec* h, cfsec_shard* shards, int n, int nbids, const int* bad_idx,
                                const int* bad_off, int verify, int mem, int* status);
 int cfsec_ec_set_devices(cfsec_ec* h, const int* devices, int ndev);
+/* access's degraded reads as one call (stream_get.go:420-431): item i is the n shards at shards[i*n ..]
+ * (each item its own segment length) with bad indices bad_idx[bad_off[i] .. bad_off[i+1]); per item
+ * exactly encoder.ReconstructData(shards_i, bad_i) -- encoder.go:146-151, lrcencoder.go:188-201 (LRC
+ * modes: n = N+M or N+M+L, the global bad indices only, fillFullShards over the first N+M shards).
+ * status[i] is what cfsec_ec_reconstruct_data returns for item i alone; the buffers of a failed item
+ * are not touched, an item with no bad data shard is a no-op, nothing but the bad data shards is
+ * written (bad parity shards keep len 0).  One concurrency slot for the call; synchronous, no checksum
+ * form.  Memory and devices as for cfsec_rs_*_stripes; launches as cfsec_rs_reconstruct_data_stripes. */
+int cfsec_ec_reconstruct_data_batch(cfsec_ec* h, cfsec_shard* shards, int n, int nitems, const int* bad_idx,
+                                    const int* bad_off, int mem, int* status);
 /* access's Put over a batch of blobs (stream_put.go:104-143 encodes them one by one): for stripe s
  * (the n shards at shards[s*n ..]) exactly encoder.Encode(shards_s), EnableVerify included; LRC
  * modes as one fused (M+L) x N pass (lrcencoder.go:35-82).  status[s]: Encode's result (CFSEC_ERR_VERIFY
