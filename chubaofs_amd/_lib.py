@@ -53,11 +53,12 @@ ErrDevice = _mk("ErrDevice", 13, "HIP runtime failure")
 ErrNotSupported = _mk("ErrNotSupported", 14, "reedsolomon.ErrNotSupported")
 ErrInvalidBlock = _mk("ErrInvalidBlock", 15, "crc32block.ErrInvalidBlock")
 ErrMismatchedCrc = _mk("ErrMismatchedCrc", 16, "crc32block.ErrMismatchedCrc")
+ErrInvalidInput = _mk("ErrInvalidInput", 17, "reedsolomon.ErrInvalidInput")
 
 _BY_CODE = {c.status: c for c in (
     ErrTooFewShards, ErrShardNoData, ErrShardSize, ErrInvShardNum, ErrMaxShardNum, ErrShortData,
     ErrReconstructRequired, ErrSingular, ErrInvalidCodeMode, ErrVerify, ErrInvalidShards,
-    ErrInvalidArg, ErrDevice, ErrNotSupported, ErrInvalidBlock, ErrMismatchedCrc)}
+    ErrInvalidArg, ErrDevice, ErrNotSupported, ErrInvalidBlock, ErrMismatchedCrc, ErrInvalidInput)}
 
 
 def check(status: int) -> None:
@@ -90,9 +91,13 @@ SIGNATURES = {
     "cfsec_rs_verify": ([_V, P_SHARD, _I, _I, _V, _P(_I)], _I),
     "cfsec_rs_reconstruct": ([_V, P_SHARD, _I, _I, _V], _I),
     "cfsec_rs_reconstruct_data": ([_V, P_SHARD, _I, _I, _V], _I),
+    "cfsec_rs_encode_idx": ([_V, P_SHARD, _I, P_SHARD, _I, _I, _V], _I),
+    "cfsec_rs_update": ([_V, P_SHARD, _I, P_SHARD, _I, _I, _V], _I),
+    "cfsec_rs_reconstruct_some": ([_V, P_SHARD, _I, _V, _I, _I, _V], _I),
     "cfsec_rs_split": ([_V, _V, _S, _S, P_SHARD, _V, _S, _P(_S)], _I),
     "cfsec_rs_join": ([_V, _V, _S, P_SHARD, _I, _S], _I),
     "cfsec_rs_encode_batch": ([_V, _V, _S, _I, _V], _I),
+    "cfsec_rs_update_batch": ([_V, _V, _V, _V, _I, _S, _I, _V], _I),
     "cfsec_rs_verify_batch": ([_V, _V, _S, _I, _V, _V], _I),
     "cfsec_rs_reconstruct_batch": ([_V, _V, _S, _I, _V, _I, _I, _V], _I),
     "cfsec_rs_encode_crc": ([_V, P_SHARD, _I, _I, _V, _V], _I),
@@ -105,6 +110,7 @@ SIGNATURES = {
     "cfsec_rs_verify_stripes": ([_V, P_SHARD, _I, _I, _V], _I),
     "cfsec_rs_reconstruct_stripes": ([_V, P_SHARD, _I, _I, _I, _V], _I),
     "cfsec_rs_reconstruct_data_stripes": ([_V, P_SHARD, _I, _I, _V], _I),
+    "cfsec_rs_reconstruct_some_stripes": ([_V, P_SHARD, _I, _V, _I, _V], _I),
     "cfsec_codemode_tactic": ([_I, _P(TacticC)], _I),
     "cfsec_ec_new": ([_P(TacticC), _I, _I, _I, _P(_V)], _I),
     "cfsec_ec_free": ([_V], None),

@@ -657,6 +657,82 @@ Status RSEngine::reconstruct_data_stripes(cfsec_shard* const* stripes, int nst, 
   return run_stripes(tasks, mem, nullptr, nullptr, /*mix=*/true);
 }
 
+Status RSEngine::reconstruct_some_stripes(cfsec_shard* const* stripes, int nst, const uint8_t* required, int mem,
+                                          int* status) {
+  if (nst < 0 || (nst > 0 && (!stripes || !status || !required))) return CFSEC_ERR_INVALID_ARG;
+  PlanStore store;
+  std::vector<StripeTask> tasks;
+  tasks.reserve((size_t)nst);
+  // a stripe's plan: the rows of its pattern's (cached) data-only plan that its mask selects, built
+  // once per (pattern, selection) of the call
+  std::map<std::pair<const StripePlan*, std::vector<bool>>, const StripePlan*> cuts;
+  std::vector<bool> present(total()), last_present, pick, last_pick;
+  const StripePlan *base = nullptr, *plan = nullptr;  // of the previous stripe that was planned
+  for (int s = 0; s < nst; ++s) {
+    status[s] = CFSEC_OK;
+    cfsec_shard* sh = stripes[s];
+    const uint8_t* req = required + (size_t)s * k_;
+    size_t S = 0;
+    Status st = sh ? check_shards(sh, total(), true, &S) : CFSEC_ERR_INVALID_ARG;
+    if (st != CFSEC_OK) {
+      status[s] = st;
+      continue;
+    }
+    int np = 0, dp = 0, missing_required = 0;
+    for (int i = 0; i < total(); ++i) {
+      present[i] = sh[i].len != 0;
+      np += present[i] ? 1 : 0;
+      dp += present[i] && i < k_ ? 1 : 0;
+      missing_required += !present[i] && i < k_ && req[i] ? 1 : 0;
+    }
+    if (np == total() || dp == k_ || missing_required == 0) continue;  // KRS/reedsolomon.go:1438-1441
+    if (np < k_) {
+      status[s] = CFSEC_ERR_TOO_FEW_SHARDS;
+      continue;
+    }
+    // batches mostly repeat one erasure pattern and one mask: the previous stripe's plans come first
+    if (!base || present != last_present) {
+      base = cached_plan(present, false, false, nullptr, &store, &st, /*data_only=*/true);
+      last_present = present;
+      plan = nullptr;
+      if (!base) {
+        status[s] = st;
+        continue;
+      }
+    }
+    pick.resize(base->out.size());
+    for (size_t o = 0; o < base->out.size(); ++o) pick[o] = req[base->out[o]] != 0;
+    if (!plan || pick != last_pick) {
+      last_pick = pick;
+      const StripePlan*& cut_plan = cuts[{base, pick}];
+      if (!cut_plan) {
+        StripePlan cut;
+        cut.in = base->in;
+        for (size_t o = 0; o < base->out.size(); ++o)
+          if (pick[o]) cut.out.push_back(base->out[o]);
+        cut.nstore = (int)cut.out.size();
+        cut.rows = Matrix(cut.nstore, k_);
+        for (size_t o = 0, j = 0; o < base->out.size(); ++o)
+          if (pick[o]) std::memcpy(cut.rows.row((int)j++), base->rows.row((int)o), k_);
+        cut_plan = store.add(cut);
+      }
+      plan = cut_plan;
+    }
+    for (int r = 0; r < plan->nstore && st == CFSEC_OK; ++r)
+      if (!sh[plan->out[r]].data || sh[plan->out[r]].cap < S) st = CFSEC_ERR_INVALID_ARG;
+    for (int c : plan->in)
+      if (!sh[c].data) st = CFSEC_ERR_INVALID_ARG;
+    if (st != CFSEC_OK) {
+      set_last_error("reconstruct batch: stripe " + std::to_string(s) + " has a missing shard with cap < shard size");
+      status[s] = st;
+      continue;
+    }
+    for (int r = 0; r < plan->nstore; ++r) sh[plan->out[r]].len = S;
+    tasks.push_back(StripeTask{sh, plan, S, &status[s], 0, 0, s});
+  }
+  return run_stripes(tasks, mem, nullptr, nullptr, /*mix=*/true);
+}
+
 void RSEngine::plan_reconstruct_tasks(cfsec_shard* const* stripes, int nst, bool verify, int* status, int phase,
                                       int owner0, PlanStore* store, std::vector<StripeTask>* tasks,
                                       const ExtraRows* extra, const std::vector<bool>* fuse, bool data_only) {

@@ -197,7 +197,7 @@ int crc32block_call(bool encode, const uint8_t* src, int64_t src_len, int64_t si
 
 extern "C" {
 
-const char* cfsec_version(void) { return "cfsec 0.5.0 (gfx950)"; }
+const char* cfsec_version(void) { return "cfsec 0.5.1 (gfx950)"; }
 
 const char* cfsec_last_error(void) { return cfsec::last_error_cstr(); }
 
@@ -220,6 +220,7 @@ const char* cfsec_status_name(int status) {
     case CFSEC_ERR_NOT_SUPPORTED: return "ErrNotSupported";
     case CFSEC_ERR_INVALID_BLOCK: return "ErrInvalidBlock";
     case CFSEC_ERR_MISMATCHED_CRC: return "ErrMismatchedCrc";
+    case CFSEC_ERR_INVALID_INPUT: return "ErrInvalidInput";
     default: return "ErrUnknown";
   }
 }
@@ -284,6 +285,24 @@ int cfsec_rs_reconstruct_data(cfsec_rs* h, cfsec_shard* shards, int n, int mem, 
   return guarded([&] { return h->e->reconstruct(shards, n, true, mem, as_stream(stream)); });
 }
 
+int cfsec_rs_encode_idx(cfsec_rs* h, const cfsec_shard* data_shard, int idx, cfsec_shard* parity, int nparity,
+                        int mem, void* stream) {
+  if (!h) return CFSEC_ERR_INVALID_ARG;
+  return guarded([&] { return h->e->encode_idx(data_shard, idx, parity, nparity, mem, as_stream(stream)); });
+}
+
+int cfsec_rs_update(cfsec_rs* h, cfsec_shard* shards, int n, const cfsec_shard* new_data, int nnew, int mem,
+                    void* stream) {
+  if (!h) return CFSEC_ERR_INVALID_ARG;
+  return guarded([&] { return h->e->update(shards, n, new_data, nnew, mem, as_stream(stream)); });
+}
+
+int cfsec_rs_reconstruct_some(cfsec_rs* h, cfsec_shard* shards, int n, const uint8_t* required, int nrequired,
+                              int mem, void* stream) {
+  if (!h) return CFSEC_ERR_INVALID_ARG;
+  return guarded([&] { return h->e->reconstruct_some(shards, n, required, nrequired, mem, as_stream(stream)); });
+}
+
 int cfsec_rs_split(cfsec_rs* h, uint8_t* data, size_t len, size_t cap, cfsec_shard* out,
                    uint8_t* pad, size_t pad_len, size_t* pad_needed) {
   if (!h) return CFSEC_ERR_INVALID_ARG;
@@ -300,6 +319,13 @@ int cfsec_rs_encode_batch(cfsec_rs* h, uint8_t* const* ptrs, size_t shard_size, 
                           void* stream) {
   if (!h) return CFSEC_ERR_INVALID_ARG;
   return guarded([&] { return h->e->encode_batch(ptrs, shard_size, nstripes, as_stream(stream)); });
+}
+
+int cfsec_rs_update_batch(cfsec_rs* h, uint8_t* const* ptrs, uint8_t* const* new_ptrs, const int* cols, int ncols,
+                          size_t shard_size, int nstripes, void* stream) {
+  if (!h) return CFSEC_ERR_INVALID_ARG;
+  return guarded(
+      [&] { return h->e->update_batch(ptrs, new_ptrs, cols, ncols, shard_size, nstripes, as_stream(stream)); });
 }
 
 int cfsec_rs_verify_batch(cfsec_rs* h, uint8_t* const* ptrs, size_t shard_size, int nstripes,
@@ -393,6 +419,16 @@ int cfsec_rs_reconstruct_stripes(cfsec_rs* h, cfsec_shard* shards, int nstripes,
   return guarded([&] {
     auto v = stripe_views(shards, nstripes, h->e->total());
     return h->e->reconstruct_stripes(v.data(), nstripes, mem, verify != 0, status);
+  });
+}
+
+int cfsec_rs_reconstruct_some_stripes(cfsec_rs* h, cfsec_shard* shards, int nstripes, const uint8_t* required, int mem,
+                                      int* status) {
+  if (!h || nstripes < 0 || (nstripes > 0 && (!shards || !status || !required))) return CFSEC_ERR_INVALID_ARG;
+  if (nstripes == 0) return CFSEC_OK;
+  return guarded([&] {
+    auto v = stripe_views(shards, nstripes, h->e->total());
+    return h->e->reconstruct_some_stripes(v.data(), nstripes, required, mem, status);
   });
 }
 

@@ -970,6 +970,143 @@ Status RSEngine::reconstruct(cfsec_shard* shards, int n, bool data_only, int mem
   return run(plan.rows, ins, outs, S, mem, stream, MatVecMode::kStore, nullptr);
 }
 
+Status RSEngine::reconstruct_some(cfsec_shard* shards, int n, const uint8_t* required, int nrequired, int mem,
+                                  hipStream_t stream) {
+  // KRS/reedsolomon.go:1407-1529 with dataOnly and a required mask
+  if (!shards || n != total() || nrequired < k_) return CFSEC_ERR_TOO_FEW_SHARDS;
+  if (!required) return CFSEC_ERR_INVALID_ARG;
+  size_t S = 0;
+  Status st = check_shards(shards, n, true, &S);
+  if (st != CFSEC_OK) return st;
+  const auto req = [&](int i) { return i < nrequired && required[i] != 0; };
+  std::vector<bool> present(n);
+  int npresent = 0, dpresent = 0, missing_required = 0;
+  for (int i = 0; i < n; ++i) {
+    present[i] = shards[i].len != 0;
+    if (present[i]) {
+      ++npresent;
+      if (i < k_) ++dpresent;
+    } else if (req(i)) {
+      ++missing_required;  // (:1427-1429: a missing parity index counts too, though parity is never rebuilt)
+    }
+  }
+  if (npresent == n || dpresent == k_ || missing_required == 0) return CFSEC_OK;
+  if (npresent < k_) return CFSEC_ERR_TOO_FEW_SHARDS;
+  ReconPlan plan;
+  st = plan_reconstruct(present, true, &plan);
+  if (st != CFSEC_OK) return st;
+  // the rows of the data-only plan that the mask selects (:1508-1512)
+  std::vector<int> picked;
+  for (size_t o = 0; o < plan.outputs.size(); ++o)
+    if (req(plan.outputs[o])) picked.push_back((int)o);
+  Matrix rows((int)picked.size(), k_);
+  std::vector<cfsec_shard*> ins, outs;
+  for (size_t j = 0; j < picked.size(); ++j) {
+    const int idx = plan.outputs[picked[j]];
+    if (!shards[idx].data || shards[idx].cap < S) {
+      set_last_error("reconstruct: missing shard " + std::to_string(idx) + " has cap < shard size");
+      return CFSEC_ERR_INVALID_ARG;
+    }
+    std::memcpy(rows.row((int)j), plan.rows.row(picked[j]), k_);
+    outs.push_back(&shards[idx]);
+  }
+  for (int v : plan.valid) ins.push_back(&shards[v]);
+  for (auto* o : outs) o->len = S;
+  return run(rows, ins, outs, S, mem, stream, MatVecMode::kStore, nullptr);
+}
+
+Status RSEngine::run_delta(const Matrix& coef, const std::vector<uint8_t*>& olds, const std::vector<uint8_t*>& news,
+                           const std::vector<uint8_t*>& outs, size_t S, int mem, hipStream_t stream) {
+  if (olds.empty() || outs.empty() || S == 0) return CFSEC_OK;
+  if (!ctx_) {
+    set_last_error("no HIP device available to the cfsec engine");
+    return CFSEC_ERR_DEVICE;
+  }
+  if (mem != CFSEC_MEM_HOST && mem != CFSEC_MEM_DEVICE) return CFSEC_ERR_INVALID_ARG;
+  std::vector<uint8_t*> all(olds);  // the call's rows: the columns, their new contents, the outputs
+  all.insert(all.end(), news.begin(), news.end());
+  all.insert(all.end(), outs.begin(), outs.end());
+  for (uint8_t* p : all)
+    if (!p) return CFSEC_ERR_INVALID_ARG;
+  const int nc = (int)olds.size(), nn = (int)news.size(), n = (int)all.size();
+  if (coef.rows != (int)outs.size() || coef.cols != nc || (nn != 0 && nn != nc)) return CFSEC_ERR_INVALID_ARG;
+  const bool host = mem == CFSEC_MEM_HOST;
+  std::optional<DeviceGuard> g;
+  if (host) {
+    g.emplace(ctx_->device());
+    if (!g->ok()) return hip_status(hipErrorInvalidDevice, "hipSetDevice");
+  }
+  // device memory as it is; host rows in place when every one of them is page-locked, else all staged
+  std::vector<uint8_t*> d(all);
+  bool staged = false;
+  for (int i = 0; i < n && host && !staged; ++i) staged = !device_alias(all[i], &d[i]);
+  const size_t slot = align_up(S, kSlotAlign);
+  hipStream_t s = host ? nullptr : stream;
+  SyncCall call(ctx_, staged ? slot * size_t(n) : 0, 1, s, !staged && !s);
+  if (!call.begun()) return call.status();
+  for (int i = 0; i < n && staged; ++i) {
+    d[i] = call.ws()->dbuf + slot * size_t(i);
+    call.copy(d[i], all[i], S, hipMemcpyHostToDevice);
+  }
+  DeltaJob job;
+  job.nc = nc, job.m = coef.rows, job.coef = coef.v.data(), job.len = S, job.nstripes = 1;
+  job.old = d.data();
+  job.neu = nn ? d.data() + nc : nullptr;
+  job.out = d.data() + nc + nn;
+  call.step("launch_delta", [&] { return launch_delta(job, call.stream()); });
+  for (int i = 0; i < n && staged; ++i)
+    if (i >= nc + nn || (nn && i < nc)) call.copy(all[i], d[i], S, hipMemcpyDeviceToHost);
+  return call.finish();
+}
+
+Status RSEngine::encode_idx(const cfsec_shard* data_shard, int idx, cfsec_shard* parity, int nparity, int mem,
+                            hipStream_t stream) {
+  if (nparity != m_) return CFSEC_ERR_TOO_FEW_SHARDS;
+  if (m_ == 0) return CFSEC_OK;
+  if (idx < 0 || idx >= k_) return CFSEC_ERR_INV_SHARD_NUM;
+  if (!parity) return CFSEC_ERR_INVALID_ARG;
+  size_t S = 0;
+  const Status st = check_shards(parity, nparity, false, &S);
+  if (st != CFSEC_OK) return st;
+  if (!data_shard || data_shard->len != S) return CFSEC_ERR_SHARD_SIZE;
+  Matrix coef(m_, 1);
+  std::vector<uint8_t*> outs(m_);
+  for (int r = 0; r < m_; ++r) {
+    coef.at(r, 0) = parity_.at(r, idx);
+    outs[r] = parity[r].data;
+  }
+  return run_delta(coef, {data_shard->data}, {}, outs, S, mem, stream);
+}
+
+Status RSEngine::update(cfsec_shard* shards, int n, const cfsec_shard* new_data, int nnew, int mem,
+                        hipStream_t stream) {
+  if (!shards || n != total() || nnew != k_) return CFSEC_ERR_TOO_FEW_SHARDS;
+  if (!new_data) return CFSEC_ERR_INVALID_ARG;
+  size_t S = 0, Sn = 0;
+  Status st = check_shards(shards, n, true, &S);
+  if (st == CFSEC_OK) st = check_shards(new_data, nnew, true, &Sn);
+  if (st != CFSEC_OK) return st;
+  for (int i = 0; i < k_; ++i)
+    if (new_data[i].len != 0 && shards[i].len == 0) return CFSEC_ERR_INVALID_INPUT;
+  for (int i = k_; i < n; ++i)
+    if (shards[i].len == 0) return CFSEC_ERR_INVALID_INPUT;
+  if (Sn != S) return CFSEC_ERR_SHARD_SIZE;  // (the reference never compares the two sizes: cfsec.h)
+  if (m_ == 0) return CFSEC_OK;              // :713-715: no outputs, nothing is touched
+  std::vector<int> cols;
+  for (int i = 0; i < k_; ++i)
+    if (new_data[i].len != 0) cols.push_back(i);
+  const int nc = (int)cols.size();
+  Matrix coef(m_, nc);
+  std::vector<uint8_t*> olds(nc), news(nc), outs(m_);
+  for (int j = 0; j < nc; ++j) {
+    olds[j] = shards[cols[j]].data;
+    news[j] = new_data[cols[j]].data;
+    for (int r = 0; r < m_; ++r) coef.at(r, j) = parity_.at(r, cols[j]);
+  }
+  for (int r = 0; r < m_; ++r) outs[r] = shards[k_ + r].data;
+  return run_delta(coef, olds, news, outs, S, mem, stream);
+}
+
 Status RSEngine::split(uint8_t* data, size_t len, size_t cap, cfsec_shard* out, uint8_t* pad,
                        size_t pad_len, size_t* pad_needed) {
   // KRS/reedsolomon.go:1574-1632
@@ -1096,6 +1233,27 @@ Status RSEngine::matvec_batch(const uint8_t* coef, int rows, uint8_t* const* ptr
   if (!g.ok()) return hip_status(hipErrorInvalidDevice, "hipSetDevice");
   const MatVecJob job = matvec_job(k_, rows, coef, S, nstripes, t.in.data(), t.out.data());
   return hip_status(launch_matvec(job, stream), "launch_matvec(matvec_batch)");
+}
+
+Status RSEngine::update_batch(uint8_t* const* ptrs, uint8_t* const* new_ptrs, const int* cols, int ncols, size_t S,
+                              int nstripes, hipStream_t stream) {
+  if (!ptrs || !new_ptrs || nstripes < 0 || ncols < 0 || (ncols > 0 && !cols)) return CFSEC_ERR_INVALID_ARG;
+  for (int j = 0; j < ncols; ++j)
+    if (cols[j] < 0 || cols[j] >= k_ || (j > 0 && cols[j] <= cols[j - 1])) return CFSEC_ERR_INVALID_ARG;
+  if (!ctx_) return CFSEC_ERR_DEVICE;
+  if (m_ == 0 || ncols == 0 || nstripes == 0 || S == 0) return CFSEC_OK;
+  const PtrTables t = ptr_tables(ptrs, total(), nstripes, std::vector<int>(cols, cols + ncols), index_range(k_, total()));
+  Matrix coef(m_, ncols);
+  for (int r = 0; r < m_; ++r)
+    for (int j = 0; j < ncols; ++j) coef.at(r, j) = parity_.at(r, cols[j]);
+  DeviceGuard g(ctx_->device());
+  if (!g.ok()) return hip_status(hipErrorInvalidDevice, "hipSetDevice");
+  DeltaJob job;
+  job.nc = ncols, job.m = m_, job.coef = coef.v.data(), job.len = S, job.nstripes = nstripes;
+  job.old = const_cast<uint8_t* const*>(t.in.data());  // (ptr_tables keeps its input rows as const)
+  job.neu = new_ptrs;
+  job.out = t.out.data();
+  return hip_status(launch_delta(job, stream), "launch_delta(update_batch)");
 }
 
 Status RSEngine::verify_batch(uint8_t* const* ptrs, size_t S, int nstripes, uint32_t* flags,

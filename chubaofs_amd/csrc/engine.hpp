@@ -21,6 +21,7 @@
 
 #include "../../include/cfsec.h"
 #include "gf256.hpp"
+#include "gf_delta.hpp"
 #include "kernels.hpp"
 
 namespace cfsec {
@@ -405,6 +406,17 @@ class RSEngine {
   Status encode_crc(cfsec_shard* shards, int n, int mem, hipStream_t stream, uint32_t* crcs);
   Status verify(cfsec_shard* shards, int n, int mem, hipStream_t stream, bool* ok);
   Status reconstruct(cfsec_shard* shards, int n, bool data_only, int mem, hipStream_t stream);
+  // EncodeIdx (KRS/reedsolomon.go:631-667): parity[r] ^= M[k + r][idx] * data_shard.
+  Status encode_idx(const cfsec_shard* data_shard, int idx, cfsec_shard* parity, int nparity, int mem,
+                    hipStream_t stream);
+  // Update (KRS/reedsolomon.go:672-734): for every present new_data[c], shards[c] ^= new_data[c] (the
+  // old shard is left holding the delta, as in the reference), then parity[r] ^= M[k + r][c] * shards[c].
+  Status update(cfsec_shard* shards, int n, const cfsec_shard* new_data, int nnew, int mem, hipStream_t stream);
+  // ReconstructSome (KRS/reedsolomon.go:1395-1397): the missing data shards i with required[i] only
+  // (entries from nrequired on count as false).  The decode matrix is the inversion cache's; the
+  // selected rows are copied out of it per call -- no plan is cached under the required mask.
+  Status reconstruct_some(cfsec_shard* shards, int n, const uint8_t* required, int nrequired, int mem,
+                          hipStream_t stream);
   Status split(uint8_t* data, size_t len, size_t cap, cfsec_shard* out, uint8_t* pad,
                size_t pad_len, size_t* pad_needed);
   Status join(uint8_t* dst, size_t dst_len, const cfsec_shard* shards, int n, size_t out_size);
@@ -418,6 +430,10 @@ class RSEngine {
   // the k inputs, then the rows outputs (any rows, e.g. ECEncoder::repair_rows).
   Status matvec_batch(const uint8_t* coef, int rows, uint8_t* const* ptrs, size_t S, int nstripes,
                       hipStream_t stream);
+  // Update of a device batch: columns cols[0 .. ncols) (strictly increasing) of every stripe change to
+  // new_ptrs[s * ncols + j]; ptrs as encode_batch (unchanged data columns are never dereferenced).
+  Status update_batch(uint8_t* const* ptrs, uint8_t* const* new_ptrs, const int* cols, int ncols, size_t S,
+                      int nstripes, hipStream_t stream);
   // The same with crc32.ChecksumIEEE of the shards (fused into the kernel where supported):
   // crcs = device [nstripes * total()]; encode checksums every shard, reconstruct the rebuilt ones
   // (other words 0).
@@ -449,6 +465,11 @@ class RSEngine {
   //   reconstruct_data:    ReconstructData(shards) (KRS/reedsolomon.go:1377-1397): the missing data
   //                        shards only; small segments of any erasure patterns share one mixed launch
   Status reconstruct_data_stripes(cfsec_shard* const* stripes, int nst, int mem, int* status);
+  //   reconstruct_some:    ReconstructSome(shards, required + s * k) per stripe: of the missing data
+  //                        shards only those its k-entry mask names; plans built per call (the rows of
+  //                        the cached data-only plan that the mask selects), mixed launch as above
+  Status reconstruct_some_stripes(cfsec_shard* const* stripes, int nst, const uint8_t* required, int mem,
+                                  int* status);
   // The planning half of reconstruct_stripes: checks every stripe (errors to status[s]), sets the
   // rebuilt shards' lengths and appends the tasks (phase `phase`, and phase + 1 for a split Verify)
   // that run_stripes executes; owner of stripe s = owner0 + s.
@@ -506,6 +527,12 @@ class RSEngine {
                   const std::vector<cfsec_shard*>& outs, size_t S, MatVecMode mode, bool* ok);
   // kStagedWhole: whole rows through the workspace, for the Verify of more inputs than one launch carries
   Status run_staged_verify(const Matrix& rows, const std::vector<cfsec_shard*>& all, size_t S, bool* ok);
+  // EncodeIdx / Update on one SyncCall: out[r] ^= coef[r][c] * d[c] (gf_delta.hpp), d[c] = olds[c] ^
+  // news[c] stored back to olds[c], or olds[c] itself when news is empty.  Device memory in place on the
+  // caller's stream; host rows that are all page-locked in place on a workspace stream; any other host
+  // call staged whole (every row copied in, olds -- when rewritten -- and outs copied back).
+  Status run_delta(const Matrix& coef, const std::vector<uint8_t*>& olds, const std::vector<uint8_t*>& news,
+                   const std::vector<uint8_t*>& outs, size_t S, int mem, hipStream_t stream);
   // encode_stripes (nstore = m) and verify_stripes (nstore = 0): the parity rows over whole stripes
   Status whole_stripes(cfsec_shard* const* stripes, int nst, int mem, int* status, int nstore);
   RSEngine() = default;

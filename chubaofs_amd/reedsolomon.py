@@ -67,6 +67,35 @@ class ReedSolomon:
     def ReconstructData(self, shards, stream=None) -> None:
         self._reconstruct(self._L.cfsec_rs_reconstruct_data, shards, stream)
 
+    def EncodeIdx(self, dataShard, idx: int, parity, stream=None) -> None:
+        """parity[r] ^= M[k + r][idx] * dataShard (KRS/reedsolomon.go:631-667): parity accumulates as
+        the data shards of a stripe arrive, each delivered once, into parity shards that start zeroed."""
+        d, p = Marshal([dataShard]), Marshal(list(parity))
+        if d.like is not None and p.like is not None and d.mem != p.mem:
+            raise TypeError("mixing host and device shards in one call")
+        like = p.like if p.like is not None else d.like
+        _lib.check(self._L.cfsec_rs_encode_idx(self._h, d.ptr(), idx, p.ptr(), p.n, p.mem if p.like is not None else d.mem,
+                                               stream_ptr(stream, like)))
+
+    def Update(self, shards, newDatashards, stream=None) -> None:
+        """Parity update for the data shards that change (KRS/reedsolomon.go:672-734): newDatashards
+        has data_shards entries, None or empty where a column keeps its contents.  As in the
+        reference, a changed entry of `shards` is left holding old ^ new, not the new contents."""
+        m, nw = Marshal(shards), Marshal(list(newDatashards))
+        if m.like is not None and nw.like is not None and m.mem != nw.mem:
+            raise TypeError("mixing host and device shards in one call")
+        _lib.check(self._L.cfsec_rs_update(self._h, m.ptr(), m.n, nw.ptr(), nw.n, m.mem, stream_ptr(stream, m.like)))
+
+    def ReconstructSome(self, shards, required, stream=None) -> None:
+        """Rebuild only the missing data shards i with required[i] (KRS/reedsolomon.go:1395-1397); every
+        other missing entry of `shards` stays as it is."""
+        m = Marshal(shards, fill_size=shard_size(shards))
+        req = np.ascontiguousarray(np.asarray(required, dtype=bool).astype(np.uint8))
+        st = self._L.cfsec_rs_reconstruct_some(self._h, m.ptr(), m.n, req.ctypes.data if req.size else None,
+                                               int(req.size), m.mem, stream_ptr(stream, m.like))
+        m.writeback()
+        _lib.check(st)
+
     def Split(self, data: np.ndarray, length: int | None = None):
         """Split data[:length] (cap = data.size) into views, KRS/reedsolomon.go:1574-1632."""
         if length is None:
@@ -144,6 +173,17 @@ class ReedSolomon:
         launch.  Per-stripe status codes, each what ReconstructData would raise for that stripe."""
         return self._stripes(self._L.cfsec_rs_reconstruct_data_stripes, stripes, True)
 
+    def ReconstructSomeStripes(self, stripes, required):
+        """ReconstructSome of every stripe in one call; required[s] is stripe s's mask of data_shards
+        entries.  Per-stripe status codes, each what ReconstructSome would raise for that stripe."""
+        req = np.zeros((max(len(stripes), 1), self.data_shards), np.uint8)
+        for s, r in enumerate(required):
+            r = np.asarray(r, dtype=bool)
+            if r.size != self.data_shards:
+                raise ValueError(f"every mask needs {self.data_shards} entries")
+            req[s] = r
+        return self._stripes(self._L.cfsec_rs_reconstruct_some_stripes, stripes, True, req.ctypes.data)
+
     # -- helpers / GPU batch API --
     def matrix(self) -> np.ndarray:
         out = np.zeros((self.total_shards, self.data_shards), np.uint8)
@@ -153,6 +193,14 @@ class ReedSolomon:
     def encode_batch(self, ptrs, shard_len: int, nstripes: int, stream=None) -> None:
         _lib.check(self._L.cfsec_rs_encode_batch(self._h, ptr_array(ptrs), shard_len, nstripes,
                                                  stream_ptr(stream, device=self.device)))
+
+    def update_batch(self, ptrs, new_ptrs, cols, shard_len: int, nstripes: int, stream=None) -> None:
+        """Update of a device batch (cfsec_rs_update_batch): columns `cols` (strictly increasing) of
+        every stripe change to new_ptrs[s * len(cols) + j]; ptrs as encode_batch.  The changed columns
+        are left holding old ^ new."""
+        ca = (ctypes.c_int * max(len(cols), 1))(*cols)
+        _lib.check(self._L.cfsec_rs_update_batch(self._h, ptr_array(ptrs), ptr_array(new_ptrs), ca, len(cols), shard_len,
+                                                 nstripes, stream_ptr(stream, device=self.device)))
 
     def verify_batch(self, ptrs, shard_len: int, nstripes: int, flags_ptr: int, stream=None) -> None:
         _lib.check(self._L.cfsec_rs_verify_batch(self._h, ptr_array(ptrs), shard_len, nstripes,

@@ -3,10 +3,9 @@
 //
 // It implements github.com/klauspost/reedsolomon.Encoder (the seam that
 // blobstore/common/ec/encoder.go:86 and :95 construct) over the C ABI in
-// include/cfsec.h.  The methods CubeFS calls go to libcfsec.so -- Encode, Verify, Reconstruct,
-// ReconstructData -- or, for Split and Join (host bookkeeping, no coding), stay in Go as the
-// reference writes them; EncodeIdx, ReconstructSome and Update, which CubeFS never calls, return
-// reedsolomon.ErrNotSupported.
+// include/cfsec.h.  The coding methods go to libcfsec.so -- Encode, Verify, Reconstruct,
+// ReconstructData, and EncodeIdx, ReconstructSome and Update, which today's CubeFS does not call --
+// while Split and Join (host bookkeeping, no coding) stay in Go as the reference writes them.
 //
 // Go releases.  CubeFS builds with Go 1.17 (go.mod:3, docker/Dockerfile:1), whose cgo rules forbid a
 // C array holding Go pointers.  So every call first looks for the one-allocation layout that
@@ -170,6 +169,8 @@ func toError(st C.int) error {
 		return reedsolomon.ErrReconstructRequired
 	case C.CFSEC_ERR_NOT_SUPPORTED:
 		return reedsolomon.ErrNotSupported
+	case C.CFSEC_ERR_INVALID_INPUT:
+		return reedsolomon.ErrInvalidInput
 	case C.CFSEC_ERR_DEVICE:
 		return fmt.Errorf("%w: %s", ErrDevice, C.GoString(C.cfsec_last_error()))
 	case C.CFSEC_ERR_SINGULAR:
@@ -417,16 +418,71 @@ func (e *Engine) Join(dst io.Writer, shards [][]byte, outSize int) error {
 	return nil
 }
 
+// vecAt is entry i of a C shard vector.
+func vecAt(v *C.cfsec_shard, i int) *C.cfsec_shard {
+	return (*C.cfsec_shard)(unsafe.Add(unsafe.Pointer(v), uintptr(i)*unsafe.Sizeof(*v)))
+}
+
+// EncodeIdx -- KRS/reedsolomon.go:631-667: parity[r] ^= M[k+r][idx] * dataShard.  The data shard and
+// the parity shards cross the ABI as one vector (callVec pins or stages one vector per call); a nil
+// and an empty slice both arrive as len == 0.
 func (e *Engine) EncodeIdx(dataShard []byte, idx int, parity [][]byte) error {
-	return reedsolomon.ErrNotSupported
+	all := append([][]byte{dataShard}, parity...)
+	return toError(callVec(all, func(v *C.cfsec_shard, n C.int) C.int {
+		return C.cfsec_rs_encode_idx(e.h, v, C.int(idx), vecAt(v, 1), n-1, C.CFSEC_MEM_HOST, nil)
+	}))
 }
 
+// ReconstructSome -- KRS/reedsolomon.go:1395-1397: the missing data shards with required[i] only.
+// Those shards get a buffer of the shard size when their capacity is short (as prepareMissing does
+// for ReconstructData), and only when the call will rebuild something.
 func (e *Engine) ReconstructSome(shards [][]byte, required []bool) error {
-	return reedsolomon.ErrNotSupported
+	if required == nil {
+		return e.reconstruct(shards, true)
+	}
+	if len(shards) != e.dataShards+e.parityShards || len(required) < e.dataShards {
+		return reedsolomon.ErrTooFewShards
+	}
+	req := make([]byte, len(required))
+	size, present, dataPresent, missingRequired := 0, 0, 0, 0
+	for i, s := range shards {
+		if i < len(required) && required[i] {
+			req[i] = 1
+		}
+		if len(s) != 0 {
+			if size == 0 {
+				size = len(s)
+			}
+			present++
+			if i < e.dataShards {
+				dataPresent++
+			}
+		} else if i < len(req) && req[i] != 0 {
+			missingRequired++
+		}
+	}
+	if size != 0 && present < len(shards) && dataPresent < e.dataShards && missingRequired > 0 && present >= e.dataShards {
+		for i := 0; i < e.dataShards; i++ {
+			if len(shards[i]) == 0 && req[i] != 0 && cap(shards[i]) < size {
+				shards[i] = reedsolomon.AllocAligned(1, size)[0][:0]
+			}
+		}
+	}
+	return toError(callVec(shards, func(v *C.cfsec_shard, n C.int) C.int {
+		return C.cfsec_rs_reconstruct_some(e.h, v, n, (*C.uint8_t)(unsafe.Pointer(&req[0])), C.int(len(req)),
+			C.CFSEC_MEM_HOST, nil)
+	}))
 }
 
+// Update -- KRS/reedsolomon.go:672-734.  As in the reference, a changed entry of shards is left
+// holding old ^ new.  The two vectors cross the ABI as one; a nil and an empty slice both arrive as
+// len == 0 (include/cfsec.h).
 func (e *Engine) Update(shards [][]byte, newDatashards [][]byte) error {
-	return reedsolomon.ErrNotSupported
+	all := append(append([][]byte{}, shards...), newDatashards...)
+	ns := len(shards)
+	return toError(callVec(all, func(v *C.cfsec_shard, n C.int) C.int {
+		return C.cfsec_rs_update(e.h, v, C.int(ns), vecAt(v, ns), n-C.int(ns), C.CFSEC_MEM_HOST, nil)
+	}))
 }
 
 // ---- crc32block framing (blobstore/common/crc32block) ----

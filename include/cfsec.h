@@ -7,9 +7,9 @@
  *  1. cfsec_rs_*  replaces the reedsolomon.Encoder engine that blobstore/common/ec
  *     constructs at blobstore/common/ec/encoder.go:86 (global) and :95 (local),
  *     i.e. vendor/github.com/klauspost/reedsolomon/reedsolomon.go:25-131 with the
- *     default (Vandermonde) matrix of reedsolomon.go:220-244.  Only the six methods
- *     CubeFS uses are exported (Encode, Verify, Reconstruct, ReconstructData, Split,
- *     Join), plus GPU batch entry points.
+ *     default (Vandermonde) matrix of reedsolomon.go:220-244.  The six methods CubeFS
+ *     uses are exported (Encode, Verify, Reconstruct, ReconstructData, Split, Join) and
+ *     EncodeIdx, Update and ReconstructSome, plus GPU batch entry points.
  *
  *  2. cfsec_ec_*  replaces ec.Encoder (blobstore/common/ec/encoder.go:41-62) as
  *     returned by ec.NewEncoder (encoder.go:78-112), for both the plain RS encoder
@@ -64,7 +64,8 @@ typedef enum {
   CFSEC_ERR_DEVICE = 13,               /* HIP runtime failure; see cfsec_last_error()         */
   CFSEC_ERR_NOT_SUPPORTED = 14,        /* reedsolomon.ErrNotSupported   KRS/reedsolomon.go:212  */
   CFSEC_ERR_INVALID_BLOCK = 15,        /* crc32block.ErrInvalidBlock    common/crc32block/util.go:29 */
-  CFSEC_ERR_MISMATCHED_CRC = 16        /* crc32block.ErrMismatchedCrc   common/crc32block/util.go:30 */
+  CFSEC_ERR_MISMATCHED_CRC = 16,       /* crc32block.ErrMismatchedCrc   common/crc32block/util.go:30 */
+  CFSEC_ERR_INVALID_INPUT = 17         /* reedsolomon.ErrInvalidInput   KRS/reedsolomon.go:670  */
 } cfsec_status;
 
 typedef enum { CFSEC_MEM_HOST = 0, CFSEC_MEM_DEVICE = 1 } cfsec_mem;
@@ -87,7 +88,9 @@ typedef struct cfsec_ec cfsec_ec;
 /* ---------------- library ---------------- */
 /* "cfsec MAJOR.MINOR.PATCH (gfx950)".  ABI history: 0.2.0 inserted src_len into
  * cfsec_crc32block_decode / cfsec_crc32block_decode_batch (callers built against 0.1.0 must be
- * rebuilt); 0.3.0, 0.4.0 and 0.5.0 add entry points only. */
+ * rebuilt); 0.3.0, 0.4.0 and 0.5.0 add entry points only; 0.5.1 adds cfsec_rs_encode_idx,
+ * cfsec_rs_update, cfsec_rs_reconstruct_some, cfsec_rs_reconstruct_some_stripes, cfsec_rs_update_batch
+ * and the status CFSEC_ERR_INVALID_INPUT. */
 const char* cfsec_version(void);
 /* Message for the last CFSEC_ERR_DEVICE on this thread ("" if none). */
 const char* cfsec_last_error(void);
@@ -121,6 +124,33 @@ int cfsec_rs_verify(cfsec_rs* h, cfsec_shard* shards, int n, int mem, void* stre
 /* Reconstruct / ReconstructData -- KRS/reedsolomon.go:1377-1552 */
 int cfsec_rs_reconstruct(cfsec_rs* h, cfsec_shard* shards, int n, int mem, void* stream);
 int cfsec_rs_reconstruct_data(cfsec_rs* h, cfsec_shard* shards, int n, int mem, void* stream);
+/* EncodeIdx -- KRS/reedsolomon.go:631-667: parity[r] ^= M[k+r][idx] * data_shard for the nparity ==
+ * parity_shards parity shards (all present, one size, equal to data_shard->len); the data shard is
+ * read only.  Checks in the reference's order: nparity (ErrTooFewShards), no parity shards (OK), idx
+ * (ErrInvShardNum), the parity shards (ErrShardNoData / ErrShardSize), the data shard's length
+ * (ErrShardSize). */
+int cfsec_rs_encode_idx(cfsec_rs* h, const cfsec_shard* data_shard, int idx,
+                        cfsec_shard* parity, int nparity, int mem, void* stream);
+/* Update -- KRS/reedsolomon.go:672-734: shards holds the n == data+parity shards of a stripe,
+ * new_data the nnew == data_shards new data shards, absent (len == 0) where a column does not change.
+ * For every changed column c: shards[c] ^= new_data[c], then parity[r] ^= M[k+r][c] * shards[c] for
+ * every r -- after the call the old data shard holds the delta old ^ new, not the new contents, as in
+ * the reference (:728-729); new_data is read only.  A present new_data[i] with an absent shards[i],
+ * or any absent parity shard, returns CFSEC_ERR_INVALID_INPUT.  Where the C seam decides what Go
+ * leaves to a panic: "absent" means len == 0 (Go's nil versus empty-non-nil distinction does not
+ * cross the ABI), and a present new_data[i] whose length differs from the stripe's shard size
+ * returns CFSEC_ERR_SHARD_SIZE (the reference never compares the two sizes).  Host memory that is
+ * not all page-locked is staged whole through HBM. */
+int cfsec_rs_update(cfsec_rs* h, cfsec_shard* shards, int n,
+                    const cfsec_shard* new_data, int nnew, int mem, void* stream);
+/* ReconstructSome -- KRS/reedsolomon.go:1395-1397 over :1407-1529: of the missing data shards only
+ * those i with required[i] != 0 are rebuilt (cap >= shard size, len = shard size afterwards); every
+ * other missing shard keeps len == 0 and no byte of its buffer is written; parity is never rebuilt.
+ * nrequired < data_shards returns ErrTooFewShards; entries from nrequired on count as false (the
+ * reference would index out of range).  required[i] at a missing parity index counts as a missing
+ * required shard, so it defeats the "nothing required is missing" early OK, as in the reference. */
+int cfsec_rs_reconstruct_some(cfsec_rs* h, cfsec_shard* shards, int n,
+                              const uint8_t* required, int nrequired, int mem, void* stream);
 /* Split -- KRS/reedsolomon.go:1574-1632 (host memory).  data has len/cap; the engine fills
  * out[0..total) with views into data and, when cap is short, into pad (caller-owned, at least
  * *pad_needed bytes; call once with pad == NULL to learn pad_needed), laid out as the reference's
@@ -141,6 +171,13 @@ int cfsec_rs_encode_batch(cfsec_rs* h, uint8_t* const* ptrs, size_t shard_size, 
  * (caller zeroes it). */
 int cfsec_rs_verify_batch(cfsec_rs* h, uint8_t* const* ptrs, size_t shard_size, int nstripes,
                           uint32_t* flags, void* stream);
+/* Update of a device batch, asynchronous on stream (as cfsec_rs_encode_batch): one changed
+ * column set cols[0..ncols) (strictly increasing, in [0, data_shards)) for every stripe;
+ * ptrs as cfsec_rs_encode_batch (entries of unchanged data columns are never dereferenced and
+ * may be NULL); new_ptrs[s * ncols + j] = the new contents of column cols[j] of stripe s.  As
+ * cfsec_rs_update, the changed columns are left holding old ^ new. */
+int cfsec_rs_update_batch(cfsec_rs* h, uint8_t* const* ptrs, uint8_t* const* new_ptrs,
+                          const int* cols, int ncols, size_t shard_size, int nstripes, void* stream);
 /* Rebuild the shards listed in erased[] (same pattern for every stripe) from the first
  * data_shards surviving shards, in one fused pass (missing data rows = inv(sub), missing
  * parity rows = parity * inv(sub)).  data_only = 1 rebuilds only erased data shards. */
@@ -211,6 +248,11 @@ int cfsec_rs_reconstruct_stripes(cfsec_rs* h, cfsec_shard* shards, int nstripes,
  * lengths and byte alignments run as one kernel launch where they are small (the mixed-plan
  * launch); CFSEC_MIX_MAX_LEN (bytes, read per call; 0: off) overrides the length limit. */
 int cfsec_rs_reconstruct_data_stripes(cfsec_rs* h, cfsec_shard* shards, int nstripes, int mem, int* status);
+/* ReconstructSome per stripe; required = nstripes * data_shards bytes, stripe s's mask at
+ * required[s * data_shards ..].  status[s] is what cfsec_rs_reconstruct_some returns for stripe s
+ * alone with that mask; small segments share the mixed-plan launch as above. */
+int cfsec_rs_reconstruct_some_stripes(cfsec_rs* h, cfsec_shard* shards, int nstripes,
+                                      const uint8_t* required, int mem, int* status);
 
 /* ---------------- ec.Encoder ---------------- */
 /* Code-mode table (codemode.go:26-79): fill *t for a CodeMode value; CFSEC_ERR_INVALID_CODE_MODE
