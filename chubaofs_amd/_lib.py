@@ -28,6 +28,13 @@ class TacticC(ctypes.Structure):
                 ("n", "m", "l", "az_count", "put_quorum", "get_quorum", "min_shard_size")]
 
 
+class BlkObject(ctypes.Structure):
+    """cfsec_blk_object: one framed object of a cfsec_crc32block_*_objects call."""
+
+    _fields_ = [("src", ctypes.c_void_p), ("src_len", ctypes.c_int64), ("dst", ctypes.c_void_p),
+                ("size", ctypes.c_int64), ("from_", ctypes.c_int64), ("to", ctypes.c_int64)]
+
+
 # ---- errors: 1:1 with the Go sentinels (see include/cfsec.h) ----
 class CfsecError(Exception):
     status = -1
@@ -152,6 +159,9 @@ SIGNATURES = {
     "cfsec_crc32block_encode_batch": ([_V, _V, _I, ctypes.c_int64, ctypes.c_int64, _V, _V], _I),
     "cfsec_crc32block_decode_batch": ([_V, ctypes.c_int64, _V, _I, ctypes.c_int64, ctypes.c_int64,
                                        ctypes.c_int64, ctypes.c_int64, _V, _V], _I),
+    "cfsec_crc32block_check_objects": ([_V, _I, ctypes.c_int64, _V, _V, _V, _I, _I, _V], _I),
+    "cfsec_crc32block_decode_objects": ([_V, _I, ctypes.c_int64, _V, _V, _V, _I, _I, _V], _I),
+    "cfsec_crc32block_encode_objects": ([_V, _I, ctypes.c_int64, _V, _V, _I, _I, _V], _I),
 }
 
 _LIB = None

@@ -6,6 +6,7 @@
 
 #include <cstring>
 
+#include "crc32block_objects.hpp"
 #include "engine.hpp"
 
 namespace cfsec {
@@ -190,6 +191,168 @@ int crc32block_call(bool encode, const uint8_t* src, int64_t src_len, int64_t si
       }
     }
     return st;
+  });
+}
+
+// ---- crc32block over mixed-size objects (crc32block_objects.hpp) ----
+
+// One launch's worth of objects: the ones of a call (or of a staged run of it) that need the device.
+struct BlkRun {
+  std::vector<cfsec_blk_object> t;  // the objects as the kernel addresses them
+  std::vector<size_t> who;          // the caller's index of each
+  std::vector<cfsec::BlkSpan> span;
+  std::vector<size_t> in_off, out_off;  // staged: offsets in the workspace buffer
+  size_t stage_bytes = 0;
+  void clear() {
+    t.clear(), who.clear(), span.clear(), in_off.clear(), out_off.clear();
+    stage_bytes = 0;
+  }
+};
+// Staged host objects share one workspace buffer up to this many bytes per run (a larger object goes alone).
+constexpr size_t kBlkStageRun = size_t(64) << 20;
+
+// The round trip of one run on one SyncCall: (staged: the touched bytes in,) the table packed into the
+// workspace's page-locked buffer and copied to its device twin, the launch, (staged: the results out,)
+// the result words.  o: the caller's objects, read for the staged copies.
+int blk_objects_run(cfsec::DeviceContext* ctx, int mode, BlkRun& run, const cfsec_blk_object* o, int64_t block_len,
+                    bool stage, void* stream, int* status, int64_t* bad_block, uint32_t* shard_crc) {
+  const size_t m = run.t.size();
+  const bool encode = mode == cfsec::kBlkEncode;
+  cfsec::SyncCall call(ctx, stage ? run.stage_bytes : 0, 2 * m, as_stream(stream), !stream && !stage);
+  if (!call.begun()) return call.status();
+  cfsec::DeviceContext::Workspace* ws = call.ws();
+  hipStream_t s = call.stream();
+  if (stage) {
+    for (size_t j = 0; j < m; ++j) {
+      const cfsec::BlkSpan& sp = run.span[j];
+      const cfsec_blk_object& c = o[run.who[j]];
+      uint8_t* in = ws->dbuf + run.in_off[j];
+      call.copy(in, c.src + (encode ? 0 : sp.f0), (size_t)sp.in_bytes, hipMemcpyHostToDevice);
+      // the kernel addresses a framed object from its byte 0; what is staged begins at block b0
+      run.t[j].src = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(in) - (uintptr_t)(encode ? 0 : sp.f0));
+      if (sp.out_bytes > 0) run.t[j].dst = ws->dbuf + run.out_off[j];
+    }
+  }
+  const cfsec::BlkPack sz = cfsec::pack_blk_objects(mode, run.t.data(), m, block_len, nullptr, 0);
+  if (sz.objects != m || sz.taken != m) {
+    cfsec::set_last_error("crc32block objects: the plan of a run changed between its two passes");
+    call.step("pack_blk_objects", [] { return (cfsec::Status)CFSEC_ERR_DEVICE; });
+  }
+  call.step("reserve_mix", [&] { return ctx->reserve_mix(ws, 0, sz.bytes, s); });
+  if (call.ok() && ws->mix_busy[0]) {  // the previous table is still being copied from
+    ws->mix_busy[0] = false;
+    call.step("hipEventSynchronize(blk table)", [&] { return hipEventSynchronize(ws->mix_ev[0]); });
+  }
+  const uint32_t* tabs = nullptr;
+  call.step("crc_device_tables", [&] { return cfsec::crc_device_tables(&tabs); });
+  if (call.ok()) {
+    cfsec::pack_blk_objects(mode, run.t.data(), m, block_len, ws->hmix[0], ws->mix_cap[0]);
+    cfsec::BlkHead* head = reinterpret_cast<cfsec::BlkHead*>(ws->hmix[0]);
+    head->tabs = (uint64_t)reinterpret_cast<uintptr_t>(tabs);
+    head->words = (uint64_t)reinterpret_cast<uintptr_t>(ws->dflags);
+  }
+  call.memset(ws->dflags, 0xFF, 4 * m);
+  call.memset(ws->dflags + m, 0, 4 * m);
+  call.step("hipMemcpyAsync H2D(blk table)",
+            [&] { return hipMemcpyAsync(ws->dmix[0], ws->hmix[0], sz.bytes, hipMemcpyHostToDevice, s); });
+  if (call.step("hipEventRecord(blk table)", [&] { return hipEventRecord(ws->mix_ev[0], s); })) ws->mix_busy[0] = true;
+  call.step("launch_crc32block_objects",
+            [&] { return cfsec::launch_crc32block_objects(mode, ws->dmix[0], sz.objects, sz.items, s); });
+  if (stage)
+    for (size_t j = 0; j < m; ++j)
+      if (run.span[j].out_bytes > 0)
+        call.copy(o[run.who[j]].dst, run.t[j].dst, (size_t)run.span[j].out_bytes, hipMemcpyDeviceToHost);
+  call.fetch_words(2 * m);
+  const int st = call.finish();
+  if (st != CFSEC_OK) return st;
+  for (size_t j = 0; j < m; ++j) {
+    const size_t i = run.who[j];
+    if (ws->hflags[j] != 0xFFFFFFFFu) {
+      status[i] = CFSEC_ERR_MISMATCHED_CRC;
+      if (bad_block) bad_block[i] = run.span[j].b0 + (int64_t)ws->hflags[j];
+    } else if (shard_crc && run.span[j].whole) {
+      shard_crc[i] = ws->hflags[m + j];
+    }
+  }
+  return CFSEC_OK;
+}
+
+// cfsec_crc32block_{check,decode,encode}_objects: the plan (pack_blk_objects' sizing pass: every object's
+// status, the ones to launch), then device pointers and page-locked host objects in place in one run,
+// other host memory staged through the workspace in runs of kBlkStageRun bytes.
+int crc32block_objects_call(int mode, const cfsec_blk_object* o, int n, int64_t block_len, int* status,
+                            int64_t* bad_block, uint32_t* shard_crc, int mem, int device, void* stream) {
+  if (!cfsec::crc32block_valid_len(block_len) || block_len > (int64_t(1) << 30)) return CFSEC_ERR_INVALID_BLOCK;
+  if (n < 0 || (n > 0 && (!o || !status)) || (mem != CFSEC_MEM_HOST && mem != CFSEC_MEM_DEVICE))
+    return CFSEC_ERR_INVALID_ARG;
+  for (int i = 0; i < n; ++i) {
+    status[i] = CFSEC_OK;
+    if (bad_block) bad_block[i] = -1;
+    if (shard_crc) shard_crc[i] = 0;  // crc32.ChecksumIEEE(nil)
+  }
+  const bool encode = mode == cfsec::kBlkEncode;
+  return guarded([&] {
+    cfsec::DeviceContext* ctx = nullptr;
+    BlkRun run;
+    for (size_t i0 = 0; i0 < (size_t)n;) {
+      const cfsec::BlkPack plan = cfsec::pack_blk_objects(mode, o + i0, (size_t)n - i0, block_len, nullptr, 0);
+      for (size_t i = 0; i < plan.taken; ++i) status[i0 + i] = plan.status[i];
+      if (plan.objects) {
+        if (!ctx && !(ctx = device_context(device))) return (int)CFSEC_ERR_DEVICE;
+        run.clear();
+        for (uint32_t idx : plan.index) {
+          run.who.push_back(i0 + idx);
+          run.t.push_back(o[i0 + idx]);
+          run.span.push_back(cfsec::blk_object_span(mode, o[i0 + idx], block_len));
+        }
+        bool stage = false;
+        if (mem == CFSEC_MEM_HOST) {
+          cfsec::DeviceGuard g(ctx->device());
+          if (!g.ok()) return (int)cfsec::hip_status(hipErrorInvalidDevice, "hipSetDevice");
+          for (size_t j = 0; j < run.t.size() && !stage; ++j) {
+            const cfsec::BlkSpan& sp = run.span[j];
+            const int64_t f0 = encode ? 0 : sp.f0;
+            uint8_t *pi = nullptr, *po = run.t[j].dst;
+            stage = !cfsec::device_alias(const_cast<uint8_t*>(run.t[j].src) + f0, &pi) ||
+                    (sp.out_bytes > 0 && !cfsec::device_alias(run.t[j].dst, &po));
+            run.t[j].src = reinterpret_cast<const uint8_t*>(reinterpret_cast<uintptr_t>(pi) - (uintptr_t)f0);
+            run.t[j].dst = po;
+          }
+        }
+        if (!stage) {
+          const int st = blk_objects_run(ctx, mode, run, o, block_len, false, stream, status, bad_block, shard_crc);
+          if (st != CFSEC_OK) return st;
+        } else {
+          BlkRun part;
+          const auto flush = [&] {
+            const int st = part.t.empty() ? (int)CFSEC_OK
+                                          : blk_objects_run(ctx, mode, part, o, block_len, true, stream, status,
+                                                            bad_block, shard_crc);
+            part.clear();
+            return st;
+          };
+          for (size_t j = 0; j < run.t.size(); ++j) {
+            const cfsec::BlkSpan& sp = run.span[j];
+            const size_t need = cfsec::align_up((size_t)sp.in_bytes, cfsec::kSlotAlign) +
+                                cfsec::align_up((size_t)sp.out_bytes, cfsec::kSlotAlign);
+            if (!part.t.empty() && part.stage_bytes + need > kBlkStageRun) {
+              const int st = flush();
+              if (st != CFSEC_OK) return st;
+            }
+            part.who.push_back(run.who[j]);
+            part.t.push_back(o[run.who[j]]);
+            part.span.push_back(sp);
+            part.in_off.push_back(part.stage_bytes);
+            part.out_off.push_back(part.stage_bytes + cfsec::align_up((size_t)sp.in_bytes, cfsec::kSlotAlign));
+            part.stage_bytes += need;
+          }
+          const int st = flush();
+          if (st != CFSEC_OK) return st;
+        }
+      }
+      i0 += plan.taken;
+    }
+    return (int)CFSEC_OK;
   });
 }
 
@@ -756,6 +919,21 @@ int cfsec_crc32block_decode_batch(const uint8_t* const* srcs, int64_t src_len, u
     if (st == CFSEC_OK) st = cfsec::hip_status(cfsec::launch_crc32block(j, s), "launch_crc32block");
     return st;
   });
+}
+
+int cfsec_crc32block_check_objects(const cfsec_blk_object* o, int n, int64_t block_len, int* status,
+                                   int64_t* bad_block, uint32_t* shard_crc, int mem, int device, void* stream) {
+  return crc32block_objects_call(cfsec::kBlkCheck, o, n, block_len, status, bad_block, shard_crc, mem, device, stream);
+}
+
+int cfsec_crc32block_decode_objects(const cfsec_blk_object* o, int n, int64_t block_len, int* status,
+                                    int64_t* bad_block, uint32_t* shard_crc, int mem, int device, void* stream) {
+  return crc32block_objects_call(cfsec::kBlkDecode, o, n, block_len, status, bad_block, shard_crc, mem, device, stream);
+}
+
+int cfsec_crc32block_encode_objects(const cfsec_blk_object* o, int n, int64_t block_len, int* status,
+                                    uint32_t* shard_crc, int mem, int device, void* stream) {
+  return crc32block_objects_call(cfsec::kBlkEncode, o, n, block_len, status, nullptr, shard_crc, mem, device, stream);
 }
 
 }  // extern "C"

@@ -274,5 +274,12 @@ struct Crc32BlockJob {
 };
 bool crc32block_valid_len(int64_t block_len);  // util.go:34-36
 hipError_t launch_crc32block(const Crc32BlockJob& job, hipStream_t stream);
+// Objects of mixed sizes, ranges and alignments in one launch (crc32block_objects.hip): `table` is the
+// device copy of an object table (crc32block_objects.hpp; mode 0 check, 1 decode, 2 encode) whose head
+// names the CRC table block (crc_device_tables) and the result words.  CFSEC_TRACE_BLK prints
+//   cfsec: blk objects mode=<check|decode|encode> objects=<n> items=<blocks> grid=<workgroups> resident=<as above>
+hipError_t crc_device_tables(const uint32_t** out);  // gf_crc.hip
+hipError_t launch_crc32block_objects(int mode, const uint8_t* table, uint32_t objects, uint32_t items,
+                                     hipStream_t stream);
 
 }  // namespace cfsec

@@ -546,3 +546,146 @@ func BlockDecode(framed []byte, size, from, to, blockLen int64) ([]byte, error) 
 		return out, toError(st)
 	}
 }
+
+// ---- crc32block over many objects of different sizes (cfsec_crc32block_*_objects) ----
+
+// BlockObject is one framed object of a BlockCheckObjects, BlockDecodeObjects or BlockEncodeObjects
+// call.  Src is the framed object (check, decode) or the payload (encode); Size is the payload size of
+// a framed object (encode takes len(Src)); [From, To) is the payload range Decoder.Reader(from, to)
+// would read (check, decode).  Dst, when not nil, receives the result in place -- To-From bytes on
+// decode, EncodeSize(len(Src)) bytes on encode -- and is allocated otherwise.
+type BlockObject struct {
+	Src      []byte
+	Size     int64
+	From, To int64
+	Dst      []byte
+}
+
+// BlockResult is one object's outcome: Err is nil, ErrMismatchedCrc (BadBlock is then the first
+// mismatching block, -1 otherwise), io.ErrUnexpectedEOF for a framed object that ends before the
+// blocks the range touches (as BlockDecode), or an argument error.  Crc is crc32.ChecksumIEEE of the
+// whole payload: always on encode; on check and decode when [From, To) is the whole payload and the
+// object is good, else 0.  Out is the decoded range or the framed object (nil on check).
+type BlockResult struct {
+	Err      error
+	BadBlock int64
+	Crc      uint32
+	Out      []byte
+}
+
+const (
+	blkCheck = iota
+	blkDecode
+	blkEncode
+)
+
+// blockObjects runs one *_objects call.  The descriptor array holds pointers, so it is built in C
+// memory from the vector callVec hands over (INTEGRATION.md §3a): buffers in HostAlloc memory go in as
+// they are and run in place; Go memory is pinned with Go >= 1.21 and staged through C memory before
+// that, copied back after the call.  The returned error speaks for the whole call only.
+func blockObjects(mode int, objs []BlockObject, blockLen int64) ([]BlockResult, error) {
+	if C.cfsec_crc32block_encode_size(0, C.int64_t(blockLen)) < 0 {
+		return nil, ErrInvalidBlock
+	}
+	n := len(objs)
+	res := make([]BlockResult, n)
+	if n == 0 {
+		return res, nil
+	}
+	vec := make([][]byte, 2*n) // object i: its source, then its destination
+	for i, o := range objs {
+		vec[2*i] = o.Src
+		need := int64(0)
+		switch mode {
+		case blkDecode:
+			if 0 <= o.From && o.From <= o.To && o.To <= o.Size {
+				need = o.To - o.From
+			}
+		case blkEncode:
+			need = int64(C.cfsec_crc32block_encode_size(C.int64_t(len(o.Src)), C.int64_t(blockLen)))
+		}
+		dst := o.Dst
+		if mode != blkCheck && dst == nil {
+			dst = make([]byte, need)
+		}
+		if mode != blkCheck && int64(len(dst)) < need {
+			return nil, errInvalidArg
+		}
+		vec[2*i+1] = dst
+	}
+	status := make([]C.int, n)
+	bad := make([]C.int64_t, n)
+	crc := make([]C.uint32_t, n)
+	st := callVec(vec, func(v *C.cfsec_shard, _ C.int) C.int {
+		sh := unsafe.Slice(v, 2*n)
+		arr := (*C.cfsec_blk_object)(C.calloc(C.size_t(n), C.size_t(unsafe.Sizeof(C.cfsec_blk_object{}))))
+		defer C.free(unsafe.Pointer(arr))
+		d := unsafe.Slice(arr, n)
+		for i, o := range objs {
+			d[i].src = sh[2*i].data
+			d[i].src_len = C.int64_t(len(o.Src))
+			d[i].dst = sh[2*i+1].data
+			d[i].size = C.int64_t(o.Size)
+			if mode == blkEncode {
+				d[i].size = C.int64_t(len(o.Src))
+			}
+			d[i].from, d[i].to = C.int64_t(o.From), C.int64_t(o.To)
+		}
+		// Go pointers passed as arguments to memory holding no Go pointers: legal without pinning
+		switch mode {
+		case blkCheck:
+			return C.cfsec_crc32block_check_objects(arr, C.int(n), C.int64_t(blockLen), &status[0], &bad[0], &crc[0],
+				C.CFSEC_MEM_HOST, -1, nil)
+		case blkDecode:
+			return C.cfsec_crc32block_decode_objects(arr, C.int(n), C.int64_t(blockLen), &status[0], &bad[0], &crc[0],
+				C.CFSEC_MEM_HOST, -1, nil)
+		}
+		for i := range bad {
+			bad[i] = -1
+		}
+		return C.cfsec_crc32block_encode_objects(arr, C.int(n), C.int64_t(blockLen), &status[0], &crc[0],
+			C.CFSEC_MEM_HOST, -1, nil)
+	})
+	if st == C.CFSEC_ERR_INVALID_BLOCK {
+		return nil, ErrInvalidBlock
+	}
+	if err := toError(st); err != nil {
+		return nil, err
+	}
+	for i := range res {
+		res[i] = BlockResult{BadBlock: int64(bad[i]), Crc: uint32(crc[i])}
+		switch status[i] {
+		case C.CFSEC_OK:
+			if mode != blkCheck {
+				res[i].Out = vec[2*i+1]
+			}
+		case C.CFSEC_ERR_MISMATCHED_CRC:
+			res[i].Err = ErrMismatchedCrc
+		case C.CFSEC_ERR_SHORT_DATA:
+			res[i].Err = io.ErrUnexpectedEOF
+		default:
+			res[i].Err = toError(status[i])
+		}
+	}
+	return res, nil
+}
+
+// BlockCheckObjects verifies, for every object, the blocks Decoder.Reader(From, To) would read and
+// copies nothing: blobnode's data inspect (datainspect.go:95-130) reads every shard of a chunk
+// through cs.Read into io.Discard.  One launch for all objects, whatever their sizes.
+func BlockCheckObjects(objs []BlockObject, blockLen int64) ([]BlockResult, error) {
+	return blockObjects(blkCheck, objs, blockLen)
+}
+
+// BlockDecodeObjects is BlockDecode over many objects in one launch (concurrent range Gets,
+// datafile.go:393-427); errors are per object.
+func BlockDecodeObjects(objs []BlockObject, blockLen int64) ([]BlockResult, error) {
+	return blockObjects(blkDecode, objs, blockLen)
+}
+
+// BlockEncodeObjects is BlockEncode over many payloads of different sizes in one launch: the rebuilt
+// shards of a repair tasklet (work_shard_recover.go:751, then datafile.go:345-373), each with the
+// shard checksum blobnode keeps in the footer.
+func BlockEncodeObjects(objs []BlockObject, blockLen int64) ([]BlockResult, error) {
+	return blockObjects(blkEncode, objs, blockLen)
+}

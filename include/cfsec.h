@@ -463,6 +463,41 @@ int cfsec_crc32block_decode_batch(const uint8_t* const* srcs, int64_t src_len, u
                                   int64_t size, int64_t block_len, int64_t from, int64_t to, uint32_t* bad,
                                   void* stream);
 
+/* Many framed objects of different payload sizes, ranges and alignments in one launch (blobnode's data
+ * inspect, datainspect.go:95-130; the rebuilt shards of a repair tasklet, datafile.go:345-373; concurrent
+ * range Gets, datafile.go:393-427).  One block_len per call; n is not bounded. */
+typedef struct cfsec_blk_object {
+  const uint8_t* src; /* check/decode: framed object; encode: payload */
+  int64_t src_len;    /* check/decode: readable framed bytes; encode: ignored */
+  uint8_t* dst;       /* decode: to - from bytes; encode: EncodeSize(size) bytes; check: ignored */
+  int64_t size;       /* payload bytes of this object */
+  int64_t from, to;   /* check/decode: payload range, Decoder.Reader(from, to); encode: ignored */
+} cfsec_blk_object;
+/* The contract is the single call's, per object: status[i] (host, n entries) is what
+ * cfsec_crc32block_decode / _encode returns for object i alone -- CFSEC_OK, CFSEC_ERR_MISMATCHED_CRC,
+ * CFSEC_ERR_SHORT_DATA (src_len ends before the last touched block: decided on the host, nothing of
+ * that object is read) or CFSEC_ERR_INVALID_ARG (a bad range, a negative size, a NULL pointer where one
+ * is needed).  bad_block[i] (host, may be NULL) is the absolute index of the object's first mismatching
+ * block, -1 otherwise.  A bad object never changes a neighbour's result and the call still returns
+ * CFSEC_OK; the return value speaks for the whole call only: CFSEC_ERR_INVALID_BLOCK for an invalid
+ * block_len, CFSEC_ERR_INVALID_ARG for n < 0, a NULL o (n > 0) or status, or an unknown mem,
+ * CFSEC_ERR_DEVICE for a HIP error.  The checked blocks are exactly those Decoder.Reader(from, to)
+ * touches (from == to inside a block: that block); a size-0 object is CFSEC_OK with nothing launched.
+ *   check   verifies the blocks and writes no payload: no destination, every block read once
+ *   decode  verifies and copies payload [from, to) to dst
+ *   encode  frames `size` bytes of src into dst
+ * shard_crc[i] (host, may be NULL) is crc32.ChecksumIEEE of the whole payload: always on encode; on
+ * check and decode when [from, to) == [0, size) and the object is CFSEC_OK, else 0.
+ * Synchronous.  CFSEC_MEM_DEVICE runs in place on `stream` (NULL = the engine's stream, ordered after
+ * the null stream); CFSEC_MEM_HOST with every object in cfsec_host_alloc memory runs in place; any other
+ * host memory is staged through HBM, runs of objects at a time (correct, not a fast path). */
+int cfsec_crc32block_check_objects(const cfsec_blk_object* o, int n, int64_t block_len, int* status,
+                                   int64_t* bad_block, uint32_t* shard_crc, int mem, int device, void* stream);
+int cfsec_crc32block_decode_objects(const cfsec_blk_object* o, int n, int64_t block_len, int* status,
+                                    int64_t* bad_block, uint32_t* shard_crc, int mem, int device, void* stream);
+int cfsec_crc32block_encode_objects(const cfsec_blk_object* o, int n, int64_t block_len, int* status,
+                                    uint32_t* shard_crc, int mem, int device, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
