@@ -17,6 +17,8 @@
 
 #include "engine.hpp"
 #include "gf_mix.hpp"
+#include "crc_pow.hpp"
+#include "gf_mix_crc.hpp"
 
 namespace cfsec {
 namespace {
@@ -427,6 +429,123 @@ MixPack pack_mix(const StripeTask* const* tasks, uint8_t* const* const* rows, si
   return pk;
 }
 
+namespace {
+// x^(8 * 4096 * 2^q), q < kMixCrcPow: a tile's end to the row's end over whole tiles (MixCrcHead::xpow2)
+struct MixCrcPow2 {
+  uint32_t v[kMixCrcPow];
+  MixCrcPow2() {
+    v[0] = crc_xpow(int64_t(8) * kMixTile);
+    for (int q = 1; q < kMixCrcPow; ++q) v[q] = crc_mulmod(v[q - 1], v[q - 1]);
+  }
+};
+}  // namespace
+
+MixPack pack_mix_crc(const StripeTask* const* tasks, uint8_t* const* const* rows, size_t n, size_t max_len,
+                     size_t nwords, uint64_t tabs, uint64_t crc, const std::map<int, int>* tasks_per_owner,
+                     uint8_t* dst, size_t cap) {
+  MixPack pk;
+  // an item's words have one writer: a task is taken when no other task of its item checksums
+  std::map<int, int> counted;
+  if (!tasks_per_owner) {
+    for (size_t i = 0; i < n; ++i)
+      if (tasks[i]->crc) ++counted[tasks[i]->owner];
+    tasks_per_owner = &counted;
+  }
+  // the sizing pass: which tasks go in, their tiles and rows, one coefficient block per plan
+  std::map<const StripePlan*, uint32_t> coef_at;  // plan -> byte offset within the coefficient area
+  std::vector<size_t> take;
+  size_t nrows = 0, ncoef = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const StripeTask& t = *tasks[i];
+    const StripePlan& p = *t.plan;
+    const size_t k = p.in.size(), m = p.out.size();
+    const uint64_t tiles = ((uint64_t)t.len + kMixTile - 1) / kMixTile;
+    bool ok = !p.compares() && !p.dy16 && k > 0 && k <= (size_t)kLaunchMaxRows && t.len > 0 && t.len <= max_len &&
+              t.crc == 2 && !t.crc_map && tiles <= kMixMaxTiles - pk.tiles;
+    if (ok) {
+      const auto owner = tasks_per_owner->find(t.owner);
+      ok = owner != tasks_per_owner->end() && owner->second == 1;
+    }
+    for (size_t r = 0; ok && r < k + m; ++r) {  // every word inside the call's words
+      const int64_t w = t.crc_word + (r < k ? p.in[r] : p.out[r - k]);
+      ok = w >= 0 && (uint64_t)w < nwords && (uint64_t)w <= 0xFFFFFFFFu;
+    }
+    if (!ok) {
+      pk.left.push_back(i);
+      continue;
+    }
+    take.push_back(i);
+    pk.tiles += (uint32_t)tiles;
+    nrows += k + m;
+    if (coef_at.emplace(&p, (uint32_t)ncoef).second) ncoef += align_up(k * m, 16);
+  }
+  pk.items = (uint32_t)take.size();
+  pk.plans = (uint32_t)coef_at.size();
+  MixCrcHead h{};
+  h.nitems = pk.items;
+  h.ntiles = pk.tiles;
+  h.nplans = pk.plans;
+  h.tabs = tabs;
+  h.crc = crc;
+  h.items_off = (uint32_t)sizeof(MixCrcHead);
+  const size_t rows_off = h.items_off + (size_t)pk.items * sizeof(MixCrcItem);
+  const size_t words_off = rows_off + nrows * 8;
+  const size_t map_off = words_off + nrows * 4;
+  const size_t coef_off = align_up(map_off + (size_t)pk.tiles * 4, 16);
+  pk.bytes = coef_off + ncoef;
+  if (pk.bytes > 0xFFFFFFFFu) {  // 32-bit offsets: never with kMixMaxTiles tiles of rows a launch addresses
+    pk = MixPack();
+    for (size_t i = 0; i < n; ++i) pk.left.push_back(i);
+    return pk;
+  }
+  h.rows_off = (uint32_t)rows_off;
+  h.words_off = (uint32_t)words_off;
+  h.map_off = (uint32_t)map_off;
+  h.coef_off = (uint32_t)coef_off;
+  h.bytes = (uint32_t)pk.bytes;
+  if (!dst || cap < pk.bytes || pk.items == 0) return pk;
+  static const MixCrcPow2 pow2;
+  static_assert(kMixTile <= 8192, "CrcPowTables::neg covers one tile of padding");
+  const CrcPowTables& pw = crc_pow_tables();
+  std::memcpy(h.xpow2, pow2.v, sizeof h.xpow2);
+  std::memcpy(dst, &h, sizeof h);
+  MixCrcItem* item = reinterpret_cast<MixCrcItem*>(dst + h.items_off);
+  uint64_t* row = reinterpret_cast<uint64_t*>(dst + h.rows_off);
+  uint32_t* word = reinterpret_cast<uint32_t*>(dst + h.words_off);
+  uint32_t* tile_item = reinterpret_cast<uint32_t*>(dst + h.map_off);
+  uint32_t tile = 0, at = 0;
+  for (size_t j = 0; j < take.size(); ++j) {
+    const StripeTask& t = *tasks[take[j]];
+    const StripePlan& p = *t.plan;
+    const uint32_t k = (uint32_t)p.in.size(), m = (uint32_t)p.out.size();
+    MixCrcItem it{};
+    it.len = t.len;
+    it.k = k;
+    it.m = m;
+    it.coef = h.coef_off + coef_at[&p];
+    it.rows = at;
+    it.tile0 = tile;
+    it.ntiles = (uint32_t)((t.len + kMixTile - 1) / kMixTile);
+    it.fin = crc_shift_ones_of((uint64_t)t.len >> 40 ? crc_xpow((int64_t)(8 * (uint64_t)t.len)) : crc_xpow8((int64_t)t.len));
+    it.gend = pw.neg[(uint64_t)it.ntiles * kMixTile - t.len];
+    std::memcpy(&item[j], &it, sizeof it);
+    for (uint32_t r = 0; r < k + m; ++r, ++at) {
+      row[at] = (uint64_t)(uintptr_t)rows[take[j]][r];
+      word[at] = (uint32_t)(t.crc_word + (r < k ? p.in[r] : p.out[r - k]));
+    }
+    for (uint32_t q = 0; q < it.ntiles; ++q) tile_item[tile++] = (uint32_t)j;
+  }
+  std::memset(dst + map_off + (size_t)pk.tiles * 4, 0, coef_off - (map_off + (size_t)pk.tiles * 4));
+  for (const auto& kv : coef_at) {
+    const size_t sz = kv.first->in.size() * kv.first->out.size();
+    if (sz == 0) continue;  // no output rows: checksums only
+    uint8_t* c = dst + h.coef_off + kv.second;
+    std::memcpy(c, kv.first->rows.v.data(), sz);
+    std::memset(c + sz, 0, align_up(sz, 16) - sz);
+  }
+  return pk;
+}
+
 void partition_stripes(const uint64_t* bytes, int n, int ndev, int* dev) {
   // Stripe i goes to the device whose share of the byte total holds the midpoint of stripe i's
   // bytes: contiguous, non-decreasing runs whose loads differ by at most one stripe's bytes.
@@ -614,6 +733,28 @@ Status RSEngine::whole_stripes(cfsec_shard* const* stripes, int nst, int mem, in
 
 Status RSEngine::encode_stripes(cfsec_shard* const* stripes, int nst, int mem, int* status) {
   return whole_stripes(stripes, nst, mem, status, m_);
+}
+
+Status RSEngine::encode_crc_stripes(cfsec_shard* const* stripes, int nst, int mem, int* status, uint32_t* crcs) {
+  // per stripe Encode, then crc32.ChecksumIEEE of every shard (access/stream_put.go:125-143, 249-253)
+  if (nst < 0 || (nst > 0 && (!stripes || !status || !crcs))) return CFSEC_ERR_INVALID_ARG;
+  const int n = total();
+  std::memset(crcs, 0, sizeof(uint32_t) * (size_t)nst * n);
+  CrcOut crc;
+  crc.words = crcs;
+  crc.n = (size_t)nst * n;
+  const StripePlan plan = whole_stripe_plan(k_, n, parity_, m_);
+  std::vector<StripeTask> tasks;
+  for (int s = 0; s < nst; ++s) {
+    size_t S = 0;
+    status[s] = stripes[s] ? whole_stripe_ok(stripes[s], n, &S) : CFSEC_ERR_INVALID_ARG;
+    if (status[s] != CFSEC_OK) continue;
+    tasks.push_back(StripeTask{stripes[s], &plan, S, &status[s], 0, 0, s});
+    tasks.back().crc = 2;
+    tasks.back().crc_word = (int64_t)s * n;
+  }
+  // a stripe that failed has no task: its words stay zero
+  return run_stripes(tasks, mem, nullptr, &crc, /*mix=*/false, /*mix_crc=*/true);
 }
 
 Status RSEngine::stripes_one_by_one(cfsec_shard* const* stripes, int nst, int mem, bool reconstruct, bool verify,
@@ -850,7 +991,7 @@ bool RSEngine::split_verify(const StripePlan& p) const {
 }
 
 Status RSEngine::run_stripes(std::vector<StripeTask>& tasks, int mem, const AsyncOut* async, const CrcOut* crc,
-                             bool mix) {
+                             bool mix, bool mix_crc) {
   if (tasks.empty()) return CFSEC_OK;
   if (devs_.empty()) {
     set_last_error("no HIP device available to the cfsec engine");
@@ -914,10 +1055,10 @@ Status RSEngine::run_stripes(std::vector<StripeTask>& tasks, int mem, const Asyn
   for (int d = 1; d < nd; ++d)
     if (!per[d].empty())
       threads.emplace_back([&, d] {
-        st[d] = run_device(per[d], mem, devs_[d], nullptr, crc, mix);
+        st[d] = run_device(per[d], mem, devs_[d], nullptr, crc, mix, mix_crc);
         if (st[d] != CFSEC_OK) err[d] = last_error_cstr();
       });
-  if (!per[0].empty()) st[0] = run_device(per[0], mem, devs_[0], async, crc, mix && !async);
+  if (!per[0].empty()) st[0] = run_device(per[0], mem, devs_[0], async, crc, mix && !async, mix_crc && !async);
   for (auto& th : threads) th.join();
   for (int d = 1; d < nd; ++d)
     if (st[d] != CFSEC_OK && st[0] == CFSEC_OK) {
@@ -969,6 +1110,9 @@ struct BatchRun {
   // per part (launch_mixed); 0: every task goes through the launch groups
   DeviceContext* ctx = nullptr;
   size_t mix_len = 0;
+  // the same with checksums (put batches of mixed-size blobs): tasks of at most mix_crc_len bytes that
+  // checksum every shard share one launch per part (launch_mixed's crc form); 0: the groups
+  size_t mix_crc_len = 0;
 
   Status join(int from, int to) { return lane_wait(ws->ev, lane[from], lane[to]); }
   void classify(const std::vector<StripeTask*>& tasks, int mem);
@@ -978,7 +1122,7 @@ struct BatchRun {
   Status run_phase(int ph);
   Status run_staged(const std::vector<StripeTask*>& sph);
   Status launch_part(const Part& part, hipStream_t s, bool fuse_crc);
-  Status launch_mixed(const Part& part, hipStream_t s, Part* rest, bool* split);
+  Status launch_mixed(const Part& part, hipStream_t s, bool with_crc, Part* rest, bool* split);
   Status checksum(const Part& part, const std::vector<char>& taken, hipStream_t s);
   Status gather(Status st);
   void hand_back(const std::vector<StripeTask*>& tasks);
@@ -1042,7 +1186,9 @@ Status BatchRun::begin(DeviceContext* ctx, int mem, const std::vector<StripeTask
   // instead of 224 us: the cross-stream wait costs more than the 10 KiB fill it hides).  When the
   // first launch is a 16x16-dyadic repair (C5's tasklet) its workgroup (0, 0) zeroes the words and
   // the memset launch goes (zero_first, handed to launch_part).
-  if (sums && nlanes == 1 && nphase == 1 && !direct.tasks.empty()) {
+  // (not in a run that may send a mixed launch with checksums first: that launch XORs into the words
+  // and zeroes nothing)
+  if (sums && nlanes == 1 && nphase == 1 && !direct.tasks.empty() && !mix_crc_len) {
     const StripeTask* t0 = direct.tasks.front();
     zero_first = t0->plan->dy16 && t0->phase == 0 && crc->n <= 0xFFFFFFFFu;
   }
@@ -1134,10 +1280,12 @@ Status BatchRun::run_staged(const std::vector<StripeTask*>& sph) {
 Status BatchRun::launch_part(const Part& whole, hipStream_t s, bool fuse_crc) {
   Status st = CFSEC_OK;
   // ReconstructData batches: the small store-only tasks, two or more, as one mixed launch whatever
-  // their plans; the rest (a lone small task too: the fixed-K kernels do that better) in groups
+  // their plans; the rest (a lone small task too: the fixed-K kernels do that better) in groups.
+  // Put batches of mixed-size blobs: the same with the launch that also checksums every shard.
   Part rest;
   bool split = false;
-  if (mix_len) st = launch_mixed(whole, s, &rest, &split);
+  if (mix_len) st = launch_mixed(whole, s, /*with_crc=*/false, &rest, &split);
+  else if (mix_crc_len && sums) st = launch_mixed(whole, s, /*with_crc=*/true, &rest, &split);
   if (st != CFSEC_OK) return st;
   const Part& part = split ? rest : whole;
   std::vector<Group> groups;
@@ -1170,6 +1318,7 @@ Status BatchRun::launch_part(const Part& whole, hipStream_t s, bool fuse_crc) {
       for (size_t i : gr.at) taken[i] = 1;
       continue;
     }
+    if (gr.plan->out.empty()) continue;  // no output rows (an engine without parity shards): checksums only
     {
       HostTimer lt("      launch_group");
       st = hip_status(launch_group(gr, ws->bflags, s), "launch_matvec(batch)");
@@ -1181,14 +1330,25 @@ Status BatchRun::launch_part(const Part& whole, hipStream_t s, bool fuse_crc) {
   return st;
 }
 
-// The tasks of a part the item table takes (pack_mix), when there are at least two, as one mixed
+// The tasks of a part the item table takes (pack_mix; with_crc: pack_mix_crc, whose launch also
+// checksums every row of its items into the call's words), when there are at least two, as one mixed
 // launch on stream s: the table packed into the lane's page-locked buffer, one copy to the device,
-// the launch.  *rest gets the other tasks (*split true); with fewer than two takers nothing is
-// launched and *split stays false.
-Status BatchRun::launch_mixed(const Part& part, hipStream_t s, Part* rest, bool* split) {
+// the launch.  *rest gets the other tasks (*split true), which go through the groups and the separate
+// checksum pass as before; with fewer than two takers nothing is launched and *split stays false.
+Status BatchRun::launch_mixed(const Part& part, hipStream_t s, bool with_crc, Part* rest, bool* split) {
   HostTimer mt("      launch_mixed");
   const size_t n = part.tasks.size();
-  const MixPack sz = pack_mix(part.tasks.data(), part.rows.data(), n, mix_len, nullptr, 0);
+  const uint32_t* tabs = nullptr;
+  if (with_crc) {
+    const Status e = hip_status(crc_device_tables(&tabs), "crc_device_tables");
+    if (e != CFSEC_OK) return e;
+  }
+  const auto pack = [&](uint8_t* dst, size_t cap) {
+    return with_crc ? pack_mix_crc(part.tasks.data(), part.rows.data(), n, mix_crc_len, crc->n,
+                                   (uint64_t)(uintptr_t)tabs, (uint64_t)(uintptr_t)dcrc, &tasks_per_owner, dst, cap)
+                    : pack_mix(part.tasks.data(), part.rows.data(), n, mix_len, dst, cap);
+  };
+  const MixPack sz = pack(nullptr, 0);
   if (sz.items < 2) return CFSEC_OK;
   const int slot = nlanes > 1 && s == lane[1] ? 1 : 0;
   Status st = ctx->reserve_mix(ws, slot, sz.bytes, s);
@@ -1198,15 +1358,18 @@ Status BatchRun::launch_mixed(const Part& part, hipStream_t s, Part* rest, bool*
     ws->mix_busy[slot] = false;
     if (st != CFSEC_OK) return st;
   }
-  const MixPack pk = pack_mix(part.tasks.data(), part.rows.data(), n, mix_len, ws->hmix[slot], ws->mix_cap[slot]);
+  const MixPack pk = pack(ws->hmix[slot], ws->mix_cap[slot]);
   st = hip_status(hipMemcpyAsync(ws->dmix[slot], ws->hmix[slot], pk.bytes, hipMemcpyHostToDevice, s),
                   "hipMemcpyAsync H2D(mix table)");
   if (st == CFSEC_OK) st = hip_status(hipEventRecord(ws->mix_ev[slot], s), "hipEventRecord(mix table)");
   ws->mix_busy[slot] = true;
-  if (st == CFSEC_OK) st = hip_status(launch_mix(ws->dmix[slot], pk.tiles, s), "launch_mix");
+  if (st == CFSEC_OK)
+    st = with_crc ? hip_status(launch_mix_crc(ws->dmix[slot], pk.tiles, s), "launch_mix_crc")
+                  : hip_status(launch_mix(ws->dmix[slot], pk.tiles, s), "launch_mix");
   const char* tr = std::getenv("CFSEC_TRACE_MATVEC");
   if (tr && tr[0] && tr[0] != '0')
-    std::fprintf(stderr, "cfsec: mix items=%u tiles=%u plans=%u\n", pk.items, pk.tiles, pk.plans);
+    std::fprintf(stderr, "cfsec: %s items=%u tiles=%u plans=%u\n", with_crc ? "mixcrc" : "mix", pk.items, pk.tiles,
+                 pk.plans);
   for (size_t i : pk.left) {
     rest->tasks.push_back(part.tasks[i]);
     rest->rows.push_back(part.rows[i]);
@@ -1277,7 +1440,7 @@ void BatchRun::hand_back(const std::vector<StripeTask*>& tasks) {
 // A batch call on one device: classify the tasks, size the lanes, acquire and zero, run the phases
 // (each: the in-place part, then the staged chunks), gather the flags, sync, hand back the results.
 Status RSEngine::run_device(std::vector<StripeTask*>& tasks, int mem, DeviceContext* ctx, const AsyncOut* async,
-                            const CrcOut* crc, bool mix) {
+                            const CrcOut* crc, bool mix, bool mix_crc) {
   HostTimer whole("  run_device");
   std::unique_ptr<HostTimer> tm(new HostTimer("    classify + acquire"));
   DeviceGuard g(ctx->device());
@@ -1285,6 +1448,7 @@ Status RSEngine::run_device(std::vector<StripeTask*>& tasks, int mem, DeviceCont
   BatchRun run{async, crc};
   run.ctx = ctx;
   run.mix_len = mix ? mix_max_len() : 0;
+  run.mix_crc_len = mix_crc ? mix_max_len() : 0;
   run.classify(tasks, mem);
   if (async && (!run.staged.empty() || (run.checks && !async->flags))) return CFSEC_ERR_INVALID_ARG;
   run.size_lanes();
@@ -1602,7 +1766,7 @@ Status LrcEncoder::reconstruct_data_batch(cfsec_shard* shards, int n, int nitems
 }
 
 Status ECEncoder::encode_batch(cfsec_shard* shards, int n, int nstripes, int mem, int* status,
-                               const AsyncOut* async, const CrcOut* crc) {
+                               const AsyncOut* async, const CrcOut* crc, bool blobs) {
   // encoder.go:114-131 per stripe: engine Encode, then Verify when EnableVerify -- the Verify pass in
   // the same call (phase 1), after the encode
   if (!shards || !status || nstripes < 0) return CFSEC_ERR_INVALID_ARG;
@@ -1650,13 +1814,13 @@ Status ECEncoder::encode_batch(cfsec_shard* shards, int n, int nstripes, int mem
     tasks.back().crc_word = (int64_t)s * n;
     if (enable_verify_ && m > 0) tasks.push_back(StripeTask{sh, &vplan, S, &status[s], 0, 1, s});
   }
-  const Status rc = engine_->run_stripes(tasks, mem, async, crc);
+  const Status rc = engine_->run_stripes(tasks, mem, async, crc, /*mix=*/false, /*mix_crc=*/blobs && crc && !async);
   clear_failed_crcs(crc, async, status, nstripes, n);
   return rc;
 }
 
 Status LrcEncoder::encode_batch(cfsec_shard* shards, int n, int nstripes, int mem, int* status,
-                                const AsyncOut* async, const CrcOut* crc) {
+                                const AsyncOut* async, const CrcOut* crc, bool blobs) {
   // lrcencoder.go:35-82 per stripe, fused: global parity and every AZ's local parity as one
   // (M+L) x N product over the data (the same rows LrcEncoder::encode launches); EnableVerify
   // compares all M+L rows in a second pass (the reference verifies the global and the local stripes)
@@ -1709,7 +1873,7 @@ Status LrcEncoder::encode_batch(cfsec_shard* shards, int n, int nstripes, int me
       tasks.push_back(v);
     }
   }
-  const Status rc = engine_->run_stripes(tasks, mem, async, crc);
+  const Status rc = engine_->run_stripes(tasks, mem, async, crc, /*mix=*/false, /*mix_crc=*/blobs && crc && !async);
   clear_failed_crcs(crc, async, status, nstripes, n);
   return rc;
 }

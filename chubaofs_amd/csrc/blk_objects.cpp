@@ -5,50 +5,21 @@
 #include <cstring>
 
 #include "crc32block_objects.hpp"
+#include "crc_pow.hpp"
 
 namespace cfsec {
-
-uint32_t crc_xpow(int64_t e);                 // gf_crc.hip: x^e mod P, any integer e
-uint32_t crc_mulmod(uint32_t a, uint32_t b);  // a * b mod P
 
 namespace {
 
 constexpr uint32_t kBlkMaxObjects = 1u << 22;  // with kBlkMaxItems: a table stays below 2^32 bytes
 constexpr int64_t kTileBytes = 4096;
 
-// Powers of x by table: a table of 1000 objects wants a few thousand of them, and square-and-multiply
-// (crc_xpow) is ~40 multiplies each.
-struct XTables {
-  uint32_t pos[5][256];  // [k][d]: x^(8 * d * 256^k)
-  uint32_t neg[8192];    // [j]: x^(-8 j)
-  XTables() {
-    for (int k = 0; k < 5; ++k) {
-      const uint32_t step = crc_xpow(int64_t(8) << (8 * k));
-      pos[k][0] = 0x80000000u;  // x^0
-      for (int d = 1; d < 256; ++d) pos[k][d] = crc_mulmod(pos[k][d - 1], step);
-    }
-    const uint32_t inv = crc_xpow(-8);
-    neg[0] = 0x80000000u;
-    for (int j = 1; j < 8192; ++j) neg[j] = crc_mulmod(neg[j - 1], inv);
-  }
-};
-const XTables& xt() {
-  static const XTables t;
-  return t;
-}
-// x^(8 n), 0 <= n < 2^40
-uint32_t xpow8(int64_t n) {
-  const XTables& t = xt();
-  uint32_t v = t.pos[0][n & 255];
-  for (int k = 1; k < 5; ++k)
-    if (const int d = (int)((n >> (8 * k)) & 255)) v = crc_mulmod(v, t.pos[k][d]);
-  return v;
-}
-uint32_t shift_ones(uint32_t xlen) { return crc_mulmod(xlen, 0xFFFFFFFFu) ^ 0xFFFFFFFFu; }
+uint32_t xpow8(int64_t n) { return crc_xpow8(n); }  // x^(8 n), 0 <= n < 2^40 (crc_pow.hpp)
+uint32_t shift_ones(uint32_t xlen) { return crc_shift_ones_of(xlen); }
 // x^(8(len + h - tiles * 4096)) with tiles = ceil((len + h) / 4096) + extra
 uint32_t tile_end_factor(int64_t len, int64_t h, int extra) {
   const int64_t tiles = (len + h + kTileBytes - 1) / kTileBytes + extra;
-  return xt().neg[tiles * kTileBytes - len - h];
+  return crc_pow_tables().neg[tiles * kTileBytes - len - h];
 }
 
 }  // namespace

@@ -568,6 +568,15 @@ int cfsec_rs_encode_stripes(cfsec_rs* h, cfsec_shard* shards, int nstripes, int 
   });
 }
 
+int cfsec_rs_encode_crc_stripes(cfsec_rs* h, cfsec_shard* shards, int nstripes, int mem, int* status,
+                                uint32_t* crcs) {
+  if (!h || nstripes < 0 || (nstripes > 0 && (!shards || !status || !crcs))) return CFSEC_ERR_INVALID_ARG;
+  return guarded([&] {
+    auto v = stripe_views(shards, nstripes, h->e->total());
+    return h->e->encode_crc_stripes(v.data(), nstripes, mem, status, crcs);
+  });
+}
+
 int cfsec_rs_verify_stripes(cfsec_rs* h, cfsec_shard* shards, int nstripes, int mem, int* status) {
   if (!h || nstripes < 0 || (nstripes > 0 && (!shards || !status))) return CFSEC_ERR_INVALID_ARG;
   return guarded([&] {
@@ -728,6 +737,14 @@ int cfsec_ec_encode_batch_crc(cfsec_ec* h, cfsec_shard* shards, int n, int nstri
   std::memset(crcs, 0, sizeof(uint32_t) * (size_t)nstripes * n);
   const cfsec::CrcOut c = crc_out(crcs, nstripes, n);
   return guarded([&] { return h->e->encode_batch(shards, n, nstripes, mem, status, nullptr, &c); });
+}
+
+int cfsec_ec_encode_blobs_crc(cfsec_ec* h, cfsec_shard* shards, int n, int nstripes, int mem, int* status,
+                              uint32_t* crcs) {
+  if (!h || nstripes < 0 || n <= 0 || (nstripes > 0 && (!shards || !status || !crcs))) return CFSEC_ERR_INVALID_ARG;
+  std::memset(crcs, 0, sizeof(uint32_t) * (size_t)nstripes * n);
+  const cfsec::CrcOut c = crc_out(crcs, nstripes, n);
+  return guarded([&] { return h->e->encode_batch(shards, n, nstripes, mem, status, nullptr, &c, /*blobs=*/true); });
 }
 
 int cfsec_ec_reconstruct_batch_async(cfsec_ec* h, cfsec_shard* shards, int n, int nbids, const int* bad_idx,

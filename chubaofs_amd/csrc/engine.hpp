@@ -375,6 +375,27 @@ MixPack pack_mix(const StripeTask* const* tasks, uint8_t* const* const* rows, si
 // distinct-pattern batch is faster mixed up to 256 KiB (0.48 / 1.07, 0.52 / 1.12, 1.00 / 1.24,
 // 2.04 / 2.15).  One limit serves both: a batch's patterns are not known to be one until it is planned.
 constexpr size_t kMixMaxLen = size_t(64) << 10;
+// The item table of a mixed-plan launch with checksums (gf_mix_crc.hpp), packed like pack_mix's from
+// the tasks that qualify: a store-only plan without a dy16 product (no output rows at all is fine: the
+// inputs are checksummed), 1 .. kLaunchMaxRows inputs, 0 < len <= max_len, every shard checksummed
+// (crc == 2) without an index remap, the only checksummed task of its item -- tasks_per_owner counts
+// the checksummed tasks per StripeTask::owner (NULL: counted over `tasks`), the rule and the reason
+// of crc_word_stride -- every word inside [0, nwords), and room left below kMixMaxTiles tiles.  The
+// table names each row's word (crc_word + shard index) and per item the two length-dependent CRC
+// constants; tabs / crc: the device addresses of the CRC table block and of word 0, stored as numbers.
+// Sizing pass, short buffer, `left` and one coefficient copy per plan as pack_mix.  Host arithmetic only.
+MixPack pack_mix_crc(const StripeTask* const* tasks, uint8_t* const* const* rows, size_t n, size_t max_len,
+                     size_t nwords, uint64_t tabs, uint64_t crc, const std::map<int, int>* tasks_per_owner,
+                     uint8_t* dst, size_t cap);
+// The route's length limit is kMixMaxLen: its rule, applied to this launch with one limit serving every
+// mode, gives 64 KiB again (tools/put_blobs_probe.py --sweep, 64 scattered blobs of ONE shard size in
+// HBM, us per blob, mixed / groups):
+//                 16 KiB        64 KiB        256 KiB       1 MiB
+//   EC12P4        1.07 / 3.72   1.49 / 3.75   3.15 / 4.01   9.56 / 6.72
+//   EC6P10L2      1.21 / 4.75   1.73 / 4.72   3.87 / 5.21   12.28 / 9.62
+//   EC6P6         0.79 / 2.38   1.41 / 2.40   3.02 / 2.89   9.00 / 6.29
+// EC6P6 is slower mixed at 256 KiB, so the largest swept length at which no mode loses is 64 KiB; no
+// point between 64 and 256 KiB was swept.
 
 // Plans built for one batch call (stable addresses for the tasks that point at them).
 struct PlanStore {
@@ -460,6 +481,10 @@ class RSEngine {
   //   reconstruct(verify): Reconstruct(shards) [then Verify(shards)], the blobnode repair step
   //                        (blobnode/work_shard_recover.go:751-760), in one fused pass
   Status encode_stripes(cfsec_shard* const* stripes, int nst, int mem, int* status);
+  //   encode_crc:          Encode(shards), then crc32.ChecksumIEEE of every shard into
+  //                        crcs[s * total() + shard] (host words; all zero for a stripe that failed);
+  //                        small stripes of any mix of lengths share one mixed launch with checksums
+  Status encode_crc_stripes(cfsec_shard* const* stripes, int nst, int mem, int* status, uint32_t* crcs);
   Status verify_stripes(cfsec_shard* const* stripes, int nst, int mem, int* status);
   Status reconstruct_stripes(cfsec_shard* const* stripes, int nst, int mem, bool verify, int* status);
   //   reconstruct_data:    ReconstructData(shards) (KRS/reedsolomon.go:1377-1397): the missing data
@@ -486,8 +511,11 @@ class RSEngine {
   // mismatches OR 1 into async->flags[owner] instead of setting the tasks' status.
   // mix (synchronous calls): small store-only tasks of a part share one mixed-plan launch
   // (BatchRun::launch_part); false: every task goes through the launch groups.
+  // mix_crc (synchronous calls): small store-only tasks that checksum every shard share one mixed-plan
+  // launch with checksums per part (pack_mix_crc's rule); false: the launch groups and their checksum
+  // routes, as every call before the put batches of mixed-size blobs.
   Status run_stripes(std::vector<StripeTask>& tasks, int mem, const AsyncOut* async = nullptr,
-                     const CrcOut* crc = nullptr, bool mix = false);
+                     const CrcOut* crc = nullptr, bool mix = false, bool mix_crc = false);
   // Plan of a Reconstruct (+ Verify) over the present shards; data_only: of a ReconstructData.
   Status plan_stripe(const std::vector<bool>& present, bool verify, StripePlan* plan,
                      const ExtraRows* extra = nullptr, bool data_only = false);
@@ -551,7 +579,7 @@ class RSEngine {
   DeviceContext* ctx_ = nullptr;
   std::vector<DeviceContext*> devs_;  // batch devices, ctx_ first
   Status run_device(std::vector<StripeTask*>& tasks, int mem, DeviceContext* ctx, const AsyncOut* async,
-                    const CrcOut* crc, bool mix);
+                    const CrcOut* crc, bool mix, bool mix_crc);
 };
 
 // The way a single-stripe call (RSEngine::run) takes, from facts gathered before anything is queued:
@@ -625,8 +653,10 @@ class ECEncoder {
   // Encode over a batch of stripes of n shards each (access puts, stream_put.go:104-143), with
   // the Config's EnableVerify; status[s] as Encode would return it.
   // crc: every shard's checksum after the Encode into crc->words[s * n + shard].
+  // blobs (with crc, synchronous): a put batch of blobs of mixed sizes -- the small stripes share one
+  // mixed launch with checksums (run_stripes' mix_crc); same results.
   virtual Status encode_batch(cfsec_shard* shards, int n, int nstripes, int mem, int* status,
-                              const AsyncOut* async = nullptr, const CrcOut* crc = nullptr);
+                              const AsyncOut* async = nullptr, const CrcOut* crc = nullptr, bool blobs = false);
   // access's degraded reads as one call (stream_get.go:420-431): item i is the n shards at
   // shards[i*n ..] with bad indices bad[bad_off[i] .. bad_off[i+1]); status[i] = what
   // reconstruct_data returns for the item alone.  One concurrency slot for the call.
@@ -661,7 +691,7 @@ class LrcEncoder : public ECEncoder {
                            bool verify, int* status, const AsyncOut* async = nullptr,
                            const CrcOut* crc = nullptr) override;
   Status encode_batch(cfsec_shard* shards, int n, int nstripes, int mem, int* status,
-                      const AsyncOut* async = nullptr, const CrcOut* crc = nullptr) override;
+                      const AsyncOut* async = nullptr, const CrcOut* crc = nullptr, bool blobs = false) override;
   Status reconstruct_data_batch(cfsec_shard* shards, int n, int nitems, const int* bad, const int* bad_off, int mem,
                                 int* status) override;
 

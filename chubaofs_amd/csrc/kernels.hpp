@@ -124,6 +124,11 @@ const char* bs_prefix_name(BsPrefix p);          // "none", "encode", "verify", 
 // the item count is unbounded and one launch carries at most kMixMaxTiles tiles.
 constexpr uint32_t kMixMaxTiles = 1u << 24;
 hipError_t launch_mix(const uint8_t* table, uint32_t ntiles, hipStream_t stream);
+// The same launch with crc32.ChecksumIEEE of every row of every item, inputs and outputs, out of the
+// product's pass (gf_mix_crc.hip): `table` is the device copy of gf_mix_crc.hpp's table (packed by
+// pack_mix_crc, engine.hpp), whose head names the CRC table block (crc_device_tables) and the checksum
+// words; each row's word is XOR-accumulated, so the caller zeroes the words first.
+hipError_t launch_mix_crc(const uint8_t* table, uint32_t ntiles, hipStream_t stream);
 
 // launch_dy16_repair's decisions, the same way: per job the table launch, per run the affine
 // bit-sliced prefix and the dyadic tail.

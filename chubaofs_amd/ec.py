@@ -109,6 +109,21 @@ class Encoder:
             return out, [[int(words[s * n + i]) for i in range(n)] for s in range(len(stripes))]
         return out
 
+    def EncodeBlobsCRC(self, stripes):
+        """EncodeBatch(stripes, crcs=True) for a put batch whose blobs differ in size: the same statuses
+        and checksums, but the stripes of up to 64 KiB per shard share one kernel launch that codes them
+        and checksums every shard, whatever their lengths (cfsec_ec_encode_blobs_crc).  Returns
+        (per-stripe status codes, per stripe the crc32.ChecksumIEEE of its n shards)."""
+        n = len(stripes[0]) if stripes else 0
+        bm = BatchMarshal(stripes, n, fill=True)
+        status = (ctypes.c_int * max(len(stripes), 1))()
+        words = (ctypes.c_uint32 * max(len(stripes) * n, 1))()
+        st = self._L.cfsec_ec_encode_blobs_crc(self._h, bm.arr, n, len(stripes), bm.mem, status, words)
+        bm.writeback()
+        _lib.check(st)
+        return ([int(status[i]) for i in range(len(stripes))],
+                [[int(words[s * n + i]) for i in range(n)] for s in range(len(stripes))])
+
     def ReconstructBatch(self, bids, badIdx, verify: bool = True, crcs: bool = False):
         """bids: list of shard lists (one per bid, all of one length n); badIdx: one index list per
         bid.  Per bid Reconstruct(shards, bad) then Verify(shards), one batched call; returns the

@@ -158,6 +158,21 @@ class ReedSolomon:
         returns one status code per stripe (0 = ok, else the code Encode would raise)."""
         return self._stripes(self._L.cfsec_rs_encode_stripes, stripes, False)
 
+    def EncodeCRCStripes(self, stripes):
+        """EncodeStripes, then crc32.ChecksumIEEE of every shard of every stripe, as access ends a put
+        (cfsec_rs_encode_crc_stripes): small stripes of any mix of lengths share one kernel launch that
+        codes and checksums them.  Returns (per-stripe status codes, per stripe its total_shards
+        checksums; all zero for a stripe that failed)."""
+        n = self.total_shards
+        bm = BatchMarshal(stripes, n, fill=False)
+        status = (ctypes.c_int * max(len(stripes), 1))()
+        words = (ctypes.c_uint32 * max(len(stripes) * n, 1))()
+        st = self._L.cfsec_rs_encode_crc_stripes(self._h, bm.arr, len(stripes), bm.mem, status, words)
+        bm.writeback()
+        _lib.check(st)
+        return ([int(status[i]) for i in range(len(stripes))],
+                [[int(words[s * n + i]) for i in range(n)] for s in range(len(stripes))])
+
     def VerifyStripes(self, stripes):
         """Per stripe: 0 when Verify holds, ErrVerify.status when it returns false, else the error."""
         return self._stripes(self._L.cfsec_rs_verify_stripes, stripes, False)

@@ -414,17 +414,34 @@ func (e *ECEncoder) RepairBatch(bids [][][]byte, badIdx [][]int, expect [][]uint
 // every stripe Encoded as Encode would (EnableVerify included; the LRC modes as one fused pass) in
 // one call; errs[s] is what Encode(stripes[s]) would have returned.
 func (e *ECEncoder) EncodeBatch(stripes [][][]byte) (errs []error, err error) {
-	errs, _, err = e.encodeBatch(stripes, false)
+	errs, _, err = e.encodeBatch(stripes, encodePlain)
 	return errs, err
 }
 
 // EncodeBatchCRC is EncodeBatch returning crc32.ChecksumIEEE of every shard of every stripe -- the
 // checksums access takes right after encoding (stream_put.go:249-253) -- from the GPU.
 func (e *ECEncoder) EncodeBatchCRC(stripes [][][]byte) ([]error, [][]uint32, error) {
-	return e.encodeBatch(stripes, true)
+	return e.encodeBatch(stripes, encodeCRC)
 }
 
-func (e *ECEncoder) encodeBatch(stripes [][][]byte, wantCRC bool) ([]error, [][]uint32, error) {
+// EncodeBlobsCRC is EncodeBatchCRC for a put batch whose blobs differ in size (a blob smaller than the
+// blob size is one stripe of its own shard size): the same errors and checksums, but the stripes of up
+// to 64 KiB per shard share one kernel launch that codes them and checksums every shard, whatever
+// their lengths (cfsec_ec_encode_blobs_crc).  Call it for a put batch of 16 or more blobs gathered across
+// requests; a batch of equal-size blobs, and a handful of blobs, are served best by EncodeBatchCRC.
+func (e *ECEncoder) EncodeBlobsCRC(blobs [][][]byte) ([]error, [][]uint32, error) {
+	return e.encodeBatch(blobs, encodeBlobsCRC)
+}
+
+// what encodeBatch calls: cfsec_ec_encode_batch, _batch_crc or _blobs_crc
+const (
+	encodePlain = iota
+	encodeCRC
+	encodeBlobsCRC
+)
+
+func (e *ECEncoder) encodeBatch(stripes [][][]byte, form int) ([]error, [][]uint32, error) {
+	wantCRC := form != encodePlain
 	errs := make([]error, len(stripes))
 	if len(stripes) == 0 {
 		return errs, nil, nil
@@ -441,8 +458,12 @@ func (e *ECEncoder) encodeBatch(stripes [][][]byte, wantCRC bool) ([]error, [][]
 	status := make([]C.int, len(stripes))
 	words := make([]C.uint32_t, len(stripes)*n+1)
 	st := callVec(flat, func(v *C.cfsec_shard, _ C.int) C.int {
-		if wantCRC {
+		switch form {
+		case encodeCRC:
 			return C.cfsec_ec_encode_batch_crc(e.h, v, C.int(n), C.int(len(stripes)), C.CFSEC_MEM_HOST, &status[0],
+				&words[0])
+		case encodeBlobsCRC:
+			return C.cfsec_ec_encode_blobs_crc(e.h, v, C.int(n), C.int(len(stripes)), C.CFSEC_MEM_HOST, &status[0],
 				&words[0])
 		}
 		return C.cfsec_ec_encode_batch(e.h, v, C.int(n), C.int(len(stripes)), C.CFSEC_MEM_HOST, &status[0])

@@ -231,6 +231,17 @@ int cfsec_rs_set_devices(cfsec_rs* h, const int* devices, int ndev);
 int cfsec_batch_partition(const uint64_t* bytes, int n, int ndev, int* dev);
 /* Encode each stripe (KRS/reedsolomon.go:609-625). */
 int cfsec_rs_encode_stripes(cfsec_rs* h, cfsec_shard* shards, int nstripes, int mem, int* status);
+/* Encode each stripe, then crc32.ChecksumIEEE of every shard, data and parity (access ends every put
+ * so: access/stream_put.go:125-143, 249-253): crcs is a host array of nstripes * (data+parity) words,
+ * indexed [stripe][shard]; a stripe whose status is not CFSEC_OK gets all-zero words and its buffers
+ * are not touched.  The batch may mix shard sizes freely: stripes of up to 64 KiB per shard, two or
+ * more, of any mix of lengths and byte alignments run as ONE kernel launch that codes and checksums
+ * them (the mixed-plan launch with checksums); longer stripes and a lone small one
+ * take the launches of cfsec_rs_encode_stripes and the checksum routes of cfsec_ec_encode_batch_crc.
+ * CFSEC_MIX_MAX_LEN (bytes, read per call; 0: off) overrides the length limit; the results do not
+ * depend on it.  An engine without parity shards checksums its data shards. */
+int cfsec_rs_encode_crc_stripes(cfsec_rs* h, cfsec_shard* shards, int nstripes, int mem, int* status,
+                                uint32_t* crcs);
 /* Verify each stripe (KRS/reedsolomon.go:770-784): status CFSEC_OK when it holds, CFSEC_ERR_VERIFY
  * when Verify would return false (no error), another code for Verify's errors. */
 int cfsec_rs_verify_stripes(cfsec_rs* h, cfsec_shard* shards, int nstripes, int mem, int* status);
@@ -301,11 +312,26 @@ int cfsec_ec_encode_batch(cfsec_ec* h, cfsec_shard* shards, int n, int nstripes,
  * ShardCrc32 of each repaired shard, blobnode/work_shard_recover.go:335-342), 0 for the others.
  * Items whose status is not CFSEC_OK get all-zero words.  Computed on the GPU from the rows the
  * product wrote (device or staged copies), before they leave HBM.  CFSEC_ERR_NOT_SUPPORTED for
- * shapes with more than 32 inputs and Verify. */
+ * shapes with more than 32 inputs and Verify.  An encoder without parity shards (M == 0) has nothing to
+ * encode: its data shards are checksummed (such a call used to fail: the empty product launch
+ * was an invalid argument). */
 int cfsec_ec_encode_batch_crc(cfsec_ec* h, cfsec_shard* shards, int n, int nstripes, int mem, int* status,
                               uint32_t* crcs);
 int cfsec_ec_reconstruct_batch_crc(cfsec_ec* h, cfsec_shard* shards, int n, int nbids, const int* bad_idx,
                                    const int* bad_off, int verify, int mem, int* status, uint32_t* crcs);
+/* cfsec_ec_encode_batch_crc for a put batch whose blobs differ in size (a blob smaller than the blob
+ * size is one stripe of its own shard size, so a batch gathered across requests is mostly small
+ * stripes of different lengths): the same contract word for word -- RS modes and LRC modes as one
+ * fused (M+L) x N pass, status[s], all-zero words for a failed stripe, EnableVerify honoured (its
+ * Verify pass runs as in cfsec_ec_encode_batch_crc) -- but the stripes of up to 64 KiB per shard, two
+ * or more, share ONE launch that codes them and checksums every shard, whatever their lengths and
+ * alignments, where cfsec_ec_encode_batch_crc takes a product launch per 18 EC12P4 stripes and a
+ * checksum launch per distinct length.  Longer stripes and a lone small one keep that call's routes.
+ * CFSEC_MIX_MAX_LEN as for cfsec_rs_reconstruct_data_stripes.  Call it for a put batch of 16 or more blobs that
+ * differ in size; a batch of equal-size blobs, and a handful of blobs (two blobs cost 10-17 us more per
+ * call here), are served best by cfsec_ec_encode_batch_crc. */
+int cfsec_ec_encode_blobs_crc(cfsec_ec* h, cfsec_shard* shards, int n, int nstripes, int mem, int* status,
+                              uint32_t* crcs);
 /* blobnode's repair of a tasklet with the checksum work around it (work_shard_recover.go:654-685,
  * 751-760, 335-342): per bid Reconstruct then Verify as cfsec_ec_reconstruct_batch(verify = 1), and
  * crcs[b*n + i] = crc32.ChecksumIEEE of shard i as it stands in the caller's memory after the call --
