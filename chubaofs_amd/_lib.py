@@ -115,6 +115,7 @@ SIGNATURES = {
     "cfsec_batch_partition": ([_V, _I, _I, _V], _I),
     "cfsec_rs_encode_stripes": ([_V, P_SHARD, _I, _I, _V], _I),
     "cfsec_rs_encode_crc_stripes": ([_V, P_SHARD, _I, _I, _V, _V], _I),
+    "cfsec_rs_repair_crc_stripes": ([_V, P_SHARD, _I, _I, _V, _V], _I),
     "cfsec_rs_verify_stripes": ([_V, P_SHARD, _I, _I, _V], _I),
     "cfsec_rs_reconstruct_stripes": ([_V, P_SHARD, _I, _I, _I, _V], _I),
     "cfsec_rs_reconstruct_data_stripes": ([_V, P_SHARD, _I, _I, _V], _I),
@@ -139,6 +140,7 @@ SIGNATURES = {
     "cfsec_ec_encode_blobs_crc": ([_V, P_SHARD, _I, _I, _I, _V, _V], _I),
     "cfsec_ec_reconstruct_batch_crc": ([_V, P_SHARD, _I, _I, _V, _V, _I, _I, _V, _V], _I),
     "cfsec_ec_repair_batch_crc": ([_V, P_SHARD, _I, _I, _V, _V, _I, _V, _V, _V, _V], _I),
+    "cfsec_ec_repair_bids_crc": ([_V, P_SHARD, _I, _I, _V, _V, _I, _V, _V, _V, _V], _I),
     "cfsec_rs_encode_contig": ([_V, _V, _S, _S, _I, _I, _V], _I),
     "cfsec_rs_verify_contig": ([_V, _V, _S, _S, _I, _I, _V, _P(_I)], _I),
     "cfsec_rs_reconstruct_contig": ([_V, _V, _S, _S, _I, _V, _I, _I, _I, _V], _I),

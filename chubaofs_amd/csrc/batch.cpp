@@ -19,6 +19,7 @@
 #include "gf_mix.hpp"
 #include "crc_pow.hpp"
 #include "gf_mix_crc.hpp"
+#include "gf_mix_sv.hpp"
 
 namespace cfsec {
 namespace {
@@ -546,6 +547,113 @@ MixPack pack_mix_crc(const StripeTask* const* tasks, uint8_t* const* const* rows
   return pk;
 }
 
+MixPack pack_mix_sv(const StripeTask* const* tasks, uint8_t* const* const* rows, const uint64_t* flags, size_t n,
+                    size_t max_len, size_t nwords, uint64_t tabs, uint64_t crc,
+                    const std::map<int, int>* tasks_per_owner, uint8_t* dst, size_t cap) {
+  MixPack pk;
+  // an item's words have one writer: a task is taken when no other task of its item checksums
+  std::map<int, int> counted;
+  if (!tasks_per_owner) {
+    for (size_t i = 0; i < n; ++i)
+      if (tasks[i]->crc) ++counted[tasks[i]->owner];
+    tasks_per_owner = &counted;
+  }
+  // the sizing pass: which tasks go in, their tiles and rows, one coefficient block per plan
+  std::map<const StripePlan*, uint32_t> coef_at;  // plan -> byte offset within the coefficient area
+  std::vector<size_t> take;
+  size_t nrows = 0, ncoef = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const StripeTask& t = *tasks[i];
+    const StripePlan& p = *t.plan;
+    const size_t k = p.in.size(), m = p.out.size();
+    const uint64_t tiles = ((uint64_t)t.len + kMixTile - 1) / kMixTile;
+    bool ok = !p.dy16 && k > 0 && k <= (size_t)kLaunchMaxRows && m > 0 && p.nstore >= 0 && (size_t)p.nstore <= m &&
+              t.len > 0 && t.len <= max_len && t.split == 0 && t.crc == 3 && !t.crc_map &&
+              tiles <= kMixMaxTiles - pk.tiles;
+    if (ok) {
+      const auto owner = tasks_per_owner->find(t.owner);
+      ok = owner != tasks_per_owner->end() && owner->second == 1;
+    }
+    for (size_t r = 0; ok && r < k + m; ++r) {  // every word inside the call's words
+      const int64_t w = t.crc_word + (r < k ? p.in[r] : p.out[r - k]);
+      ok = w >= 0 && (uint64_t)w < nwords && (uint64_t)w <= 0xFFFFFFFFu;
+    }
+    if (!ok) {
+      pk.left.push_back(i);
+      continue;
+    }
+    take.push_back(i);
+    pk.tiles += (uint32_t)tiles;
+    nrows += k + m;
+    if (coef_at.emplace(&p, (uint32_t)ncoef).second) ncoef += align_up(k * m, 16);
+  }
+  pk.items = (uint32_t)take.size();
+  pk.plans = (uint32_t)coef_at.size();
+  MixCrcHead h{};
+  h.nitems = pk.items;
+  h.ntiles = pk.tiles;
+  h.nplans = pk.plans;
+  h.tabs = tabs;
+  h.crc = crc;
+  h.items_off = (uint32_t)sizeof(MixCrcHead);
+  const size_t rows_off = h.items_off + (size_t)pk.items * sizeof(MixSvItem);
+  const size_t words_off = rows_off + nrows * 8;
+  const size_t map_off = words_off + nrows * 4;
+  const size_t coef_off = align_up(map_off + (size_t)pk.tiles * 4, 16);
+  pk.bytes = coef_off + ncoef;
+  if (pk.bytes > 0xFFFFFFFFu) {  // 32-bit offsets: never with kMixMaxTiles tiles of rows a launch addresses
+    pk = MixPack();
+    for (size_t i = 0; i < n; ++i) pk.left.push_back(i);
+    return pk;
+  }
+  h.rows_off = (uint32_t)rows_off;
+  h.words_off = (uint32_t)words_off;
+  h.map_off = (uint32_t)map_off;
+  h.coef_off = (uint32_t)coef_off;
+  h.bytes = (uint32_t)pk.bytes;
+  if (!dst || cap < pk.bytes || pk.items == 0) return pk;
+  static const MixCrcPow2 pow2;
+  const CrcPowTables& pw = crc_pow_tables();
+  std::memcpy(h.xpow2, pow2.v, sizeof h.xpow2);
+  std::memcpy(dst, &h, sizeof h);
+  uint8_t* item = dst + h.items_off;
+  uint64_t* row = reinterpret_cast<uint64_t*>(dst + h.rows_off);
+  uint32_t* word = reinterpret_cast<uint32_t*>(dst + h.words_off);
+  uint32_t* tile_item = reinterpret_cast<uint32_t*>(dst + h.map_off);
+  uint32_t tile = 0, at = 0;
+  for (size_t j = 0; j < take.size(); ++j) {
+    const StripeTask& t = *tasks[take[j]];
+    const StripePlan& p = *t.plan;
+    const uint32_t k = (uint32_t)p.in.size(), m = (uint32_t)p.out.size();
+    MixSvItem it{};
+    it.len = t.len;
+    it.k = k;
+    it.m = m;
+    it.coef = h.coef_off + coef_at[&p];
+    it.rows = at;
+    it.tile0 = tile;
+    it.ntiles = (uint32_t)((t.len + kMixTile - 1) / kMixTile);
+    it.fin = crc_shift_ones_of((uint64_t)t.len >> 40 ? crc_xpow((int64_t)(8 * (uint64_t)t.len)) : crc_xpow8((int64_t)t.len));
+    it.gend = pw.neg[(uint64_t)it.ntiles * kMixTile - t.len];
+    it.nstore = (uint32_t)p.nstore;
+    it.flag = flags ? flags[take[j]] : 0;
+    std::memcpy(item + j * sizeof it, &it, sizeof it);
+    for (uint32_t r = 0; r < k + m; ++r, ++at) {
+      row[at] = (uint64_t)(uintptr_t)rows[take[j]][r];
+      word[at] = (uint32_t)(t.crc_word + (r < k ? p.in[r] : p.out[r - k]));
+    }
+    for (uint32_t q = 0; q < it.ntiles; ++q) tile_item[tile++] = (uint32_t)j;
+  }
+  std::memset(dst + map_off + (size_t)pk.tiles * 4, 0, coef_off - (map_off + (size_t)pk.tiles * 4));
+  for (const auto& kv : coef_at) {
+    const size_t sz = kv.first->in.size() * kv.first->out.size();
+    uint8_t* c = dst + h.coef_off + kv.second;
+    std::memcpy(c, kv.first->rows.v.data(), sz);
+    std::memset(c + sz, 0, align_up(sz, 16) - sz);
+  }
+  return pk;
+}
+
 void partition_stripes(const uint64_t* bytes, int n, int ndev, int* dev) {
   // Stripe i goes to the device whose share of the byte total holds the midpoint of stripe i's
   // bytes: contiguous, non-decreasing runs whose loads differ by at most one stripe's bytes.
@@ -790,6 +898,30 @@ Status RSEngine::reconstruct_stripes(cfsec_shard* const* stripes, int nst, int m
   return run_stripes(tasks, mem);
 }
 
+Status RSEngine::repair_crc_stripes(cfsec_shard* const* stripes, int nst, int mem, int* status, uint32_t* crcs) {
+  // per stripe Reconstruct, then Verify, and crc32.ChecksumIEEE of every shard as it stands
+  // (blobnode/work_shard_recover.go:708-771, 335-342)
+  if (nst < 0 || (nst > 0 && (!stripes || !status || !crcs))) return CFSEC_ERR_INVALID_ARG;
+  if (k_ > kLaunchMaxRows && m_ > 0) return CFSEC_ERR_NOT_SUPPORTED;  // Verify there is the single-stripe path's
+  const int n = total();
+  std::memset(crcs, 0, sizeof(uint32_t) * (size_t)nst * n);
+  CrcOut crc;
+  crc.words = crcs;
+  crc.n = (size_t)nst * n;
+  crc.every = true;
+  PlanStore store;
+  std::vector<StripeTask> tasks;
+  plan_reconstruct_tasks(stripes, nst, true, status, 0, 0, &store, &tasks);
+  for (StripeTask& t : tasks) {  // every row, by the task that reads them all (a split Verify's second pass)
+    t.crc = t.split == 2 ? 0 : 3;
+    t.crc_word = (int64_t)t.owner * n;
+  }
+  const Status rc = run_stripes(tasks, mem, nullptr, &crc, /*mix=*/false, /*mix_crc=*/false, /*mix_sv=*/true);
+  for (int s = 0; s < nst; ++s)  // a stripe that failed has no checksums
+    if (status[s] != CFSEC_OK && status[s] != CFSEC_ERR_VERIFY) std::memset(crcs + (size_t)s * n, 0, sizeof(uint32_t) * n);
+  return rc;
+}
+
 Status RSEngine::reconstruct_data_stripes(cfsec_shard* const* stripes, int nst, int mem, int* status) {
   if (nst < 0 || (nst > 0 && (!stripes || !status))) return CFSEC_ERR_INVALID_ARG;
   PlanStore store;
@@ -991,7 +1123,7 @@ bool RSEngine::split_verify(const StripePlan& p) const {
 }
 
 Status RSEngine::run_stripes(std::vector<StripeTask>& tasks, int mem, const AsyncOut* async, const CrcOut* crc,
-                             bool mix, bool mix_crc) {
+                             bool mix, bool mix_crc, bool mix_sv) {
   if (tasks.empty()) return CFSEC_OK;
   if (devs_.empty()) {
     set_last_error("no HIP device available to the cfsec engine");
@@ -1055,10 +1187,11 @@ Status RSEngine::run_stripes(std::vector<StripeTask>& tasks, int mem, const Asyn
   for (int d = 1; d < nd; ++d)
     if (!per[d].empty())
       threads.emplace_back([&, d] {
-        st[d] = run_device(per[d], mem, devs_[d], nullptr, crc, mix, mix_crc);
+        st[d] = run_device(per[d], mem, devs_[d], nullptr, crc, mix, mix_crc, mix_sv);
         if (st[d] != CFSEC_OK) err[d] = last_error_cstr();
       });
-  if (!per[0].empty()) st[0] = run_device(per[0], mem, devs_[0], async, crc, mix && !async, mix_crc && !async);
+  if (!per[0].empty())
+    st[0] = run_device(per[0], mem, devs_[0], async, crc, mix && !async, mix_crc && !async, mix_sv && !async);
   for (auto& th : threads) th.join();
   for (int d = 1; d < nd; ++d)
     if (st[d] != CFSEC_OK && st[0] == CFSEC_OK) {
@@ -1113,6 +1246,11 @@ struct BatchRun {
   // the same with checksums (put batches of mixed-size blobs): tasks of at most mix_crc_len bytes that
   // checksum every shard share one launch per part (launch_mixed's crc form); 0: the groups
   size_t mix_crc_len = 0;
+  // the same with Verify in it (repair tasklets of mixed-size bids): tasks of at most mix_sv_len bytes
+  // that store, compare and checksum every shard share one launch per part (launch_mixed's sv form); 0:
+  // the groups
+  size_t mix_sv_len = 0;
+  enum MixKind { kMix, kMixCrc, kMixSv };
 
   Status join(int from, int to) { return lane_wait(ws->ev, lane[from], lane[to]); }
   void classify(const std::vector<StripeTask*>& tasks, int mem);
@@ -1122,7 +1260,7 @@ struct BatchRun {
   Status run_phase(int ph);
   Status run_staged(const std::vector<StripeTask*>& sph);
   Status launch_part(const Part& part, hipStream_t s, bool fuse_crc);
-  Status launch_mixed(const Part& part, hipStream_t s, bool with_crc, Part* rest, bool* split);
+  Status launch_mixed(const Part& part, hipStream_t s, MixKind kind, Part* rest, bool* split);
   Status checksum(const Part& part, const std::vector<char>& taken, hipStream_t s);
   Status gather(Status st);
   void hand_back(const std::vector<StripeTask*>& tasks);
@@ -1188,7 +1326,7 @@ Status BatchRun::begin(DeviceContext* ctx, int mem, const std::vector<StripeTask
   // the memset launch goes (zero_first, handed to launch_part).
   // (not in a run that may send a mixed launch with checksums first: that launch XORs into the words
   // and zeroes nothing)
-  if (sums && nlanes == 1 && nphase == 1 && !direct.tasks.empty() && !mix_crc_len) {
+  if (sums && nlanes == 1 && nphase == 1 && !direct.tasks.empty() && !mix_crc_len && !mix_sv_len) {
     const StripeTask* t0 = direct.tasks.front();
     zero_first = t0->plan->dy16 && t0->phase == 0 && crc->n <= 0xFFFFFFFFu;
   }
@@ -1282,10 +1420,12 @@ Status BatchRun::launch_part(const Part& whole, hipStream_t s, bool fuse_crc) {
   // ReconstructData batches: the small store-only tasks, two or more, as one mixed launch whatever
   // their plans; the rest (a lone small task too: the fixed-K kernels do that better) in groups.
   // Put batches of mixed-size blobs: the same with the launch that also checksums every shard.
+  // Repair tasklets of mixed-size bids: the same with the launch that also compares (Verify).
   Part rest;
   bool split = false;
-  if (mix_len) st = launch_mixed(whole, s, /*with_crc=*/false, &rest, &split);
-  else if (mix_crc_len && sums) st = launch_mixed(whole, s, /*with_crc=*/true, &rest, &split);
+  if (mix_len) st = launch_mixed(whole, s, kMix, &rest, &split);
+  else if (mix_crc_len && sums) st = launch_mixed(whole, s, kMixCrc, &rest, &split);
+  else if (mix_sv_len && sums) st = launch_mixed(whole, s, kMixSv, &rest, &split);
   if (st != CFSEC_OK) return st;
   const Part& part = split ? rest : whole;
   std::vector<Group> groups;
@@ -1330,26 +1470,49 @@ Status BatchRun::launch_part(const Part& whole, hipStream_t s, bool fuse_crc) {
   return st;
 }
 
-// The tasks of a part the item table takes (pack_mix; with_crc: pack_mix_crc, whose launch also
-// checksums every row of its items into the call's words), when there are at least two, as one mixed
-// launch on stream s: the table packed into the lane's page-locked buffer, one copy to the device,
-// the launch.  *rest gets the other tasks (*split true), which go through the groups and the separate
-// checksum pass as before; with fewer than two takers nothing is launched and *split stays false.
-Status BatchRun::launch_mixed(const Part& part, hipStream_t s, bool with_crc, Part* rest, bool* split) {
+// The tasks of a part the item table takes (pack_mix; kMixCrc: pack_mix_crc, whose launch also
+// checksums every row of its items into the call's words; kMixSv: pack_mix_sv, whose launch compares
+// rows too), when there are at least two, as one mixed launch on stream s: the table packed into the
+// lane's page-locked buffer, one copy to the device, the launch.  *rest gets the other tasks (*split
+// true), which go through the groups and the separate checksum pass as before; with fewer than two
+// takers nothing is launched and *split stays false.
+// kMixSv: a taker's Verify word is routed as the groups route theirs -- with fdirect the item's own word
+// (recorded as written directly), otherwise a per-task word and the gather.
+Status BatchRun::launch_mixed(const Part& part, hipStream_t s, MixKind kind, Part* rest, bool* split) {
   HostTimer mt("      launch_mixed");
   const size_t n = part.tasks.size();
   const uint32_t* tabs = nullptr;
-  if (with_crc) {
+  if (kind != kMix) {
     const Status e = hip_status(crc_device_tables(&tabs), "crc_device_tables");
     if (e != CFSEC_OK) return e;
   }
+  std::vector<uint64_t> fword;  // kMixSv: the address of every taker's Verify word
   const auto pack = [&](uint8_t* dst, size_t cap) {
-    return with_crc ? pack_mix_crc(part.tasks.data(), part.rows.data(), n, mix_crc_len, crc->n,
-                                   (uint64_t)(uintptr_t)tabs, (uint64_t)(uintptr_t)dcrc, &tasks_per_owner, dst, cap)
-                    : pack_mix(part.tasks.data(), part.rows.data(), n, mix_len, dst, cap);
+    if (kind == kMixSv)
+      return pack_mix_sv(part.tasks.data(), part.rows.data(), fword.empty() ? nullptr : fword.data(), n, mix_sv_len,
+                         crc->n, (uint64_t)(uintptr_t)tabs, (uint64_t)(uintptr_t)dcrc, &tasks_per_owner, dst, cap);
+    return kind == kMixCrc ? pack_mix_crc(part.tasks.data(), part.rows.data(), n, mix_crc_len, crc->n,
+                                          (uint64_t)(uintptr_t)tabs, (uint64_t)(uintptr_t)dcrc, &tasks_per_owner, dst,
+                                          cap)
+                           : pack_mix(part.tasks.data(), part.rows.data(), n, mix_len, dst, cap);
   };
   const MixPack sz = pack(nullptr, 0);
   if (sz.items < 2) return CFSEC_OK;
+  if (kind == kMixSv) {
+    std::vector<char> is_left(n, 0);
+    for (size_t i : sz.left) is_left[i] = 1;
+    fword.assign(n, 0);
+    for (size_t i = 0; i < n; ++i) {
+      if (is_left[i]) continue;
+      StripeTask* t = part.tasks[i];
+      int w = -1;  // nothing compared: no word; fdirect: the item's own word
+      if (t->plan->compares()) {
+        if (!fdirect) w = next_flag++;
+        fword[i] = (uint64_t)(uintptr_t)(fdirect ? fdirect + t->owner : ws->bflags + w);
+      }
+      flags.emplace_back(t, w);
+    }
+  }
   const int slot = nlanes > 1 && s == lane[1] ? 1 : 0;
   Status st = ctx->reserve_mix(ws, slot, sz.bytes, s);
   if (st != CFSEC_OK) return st;
@@ -1364,12 +1527,13 @@ Status BatchRun::launch_mixed(const Part& part, hipStream_t s, bool with_crc, Pa
   if (st == CFSEC_OK) st = hip_status(hipEventRecord(ws->mix_ev[slot], s), "hipEventRecord(mix table)");
   ws->mix_busy[slot] = true;
   if (st == CFSEC_OK)
-    st = with_crc ? hip_status(launch_mix_crc(ws->dmix[slot], pk.tiles, s), "launch_mix_crc")
-                  : hip_status(launch_mix(ws->dmix[slot], pk.tiles, s), "launch_mix");
+    st = kind == kMixSv    ? hip_status(launch_mix_sv(ws->dmix[slot], pk.tiles, s), "launch_mix_sv")
+         : kind == kMixCrc ? hip_status(launch_mix_crc(ws->dmix[slot], pk.tiles, s), "launch_mix_crc")
+                           : hip_status(launch_mix(ws->dmix[slot], pk.tiles, s), "launch_mix");
   const char* tr = std::getenv("CFSEC_TRACE_MATVEC");
   if (tr && tr[0] && tr[0] != '0')
-    std::fprintf(stderr, "cfsec: %s items=%u tiles=%u plans=%u\n", with_crc ? "mixcrc" : "mix", pk.items, pk.tiles,
-                 pk.plans);
+    std::fprintf(stderr, "cfsec: %s items=%u tiles=%u plans=%u\n",
+                 kind == kMixSv ? "mixsv" : kind == kMixCrc ? "mixcrc" : "mix", pk.items, pk.tiles, pk.plans);
   for (size_t i : pk.left) {
     rest->tasks.push_back(part.tasks[i]);
     rest->rows.push_back(part.rows[i]);
@@ -1440,7 +1604,7 @@ void BatchRun::hand_back(const std::vector<StripeTask*>& tasks) {
 // A batch call on one device: classify the tasks, size the lanes, acquire and zero, run the phases
 // (each: the in-place part, then the staged chunks), gather the flags, sync, hand back the results.
 Status RSEngine::run_device(std::vector<StripeTask*>& tasks, int mem, DeviceContext* ctx, const AsyncOut* async,
-                            const CrcOut* crc, bool mix, bool mix_crc) {
+                            const CrcOut* crc, bool mix, bool mix_crc, bool mix_sv) {
   HostTimer whole("  run_device");
   std::unique_ptr<HostTimer> tm(new HostTimer("    classify + acquire"));
   DeviceGuard g(ctx->device());
@@ -1449,6 +1613,7 @@ Status RSEngine::run_device(std::vector<StripeTask*>& tasks, int mem, DeviceCont
   run.ctx = ctx;
   run.mix_len = mix ? mix_max_len() : 0;
   run.mix_crc_len = mix_crc ? mix_max_len() : 0;
+  run.mix_sv_len = mix_sv ? mix_max_len() : 0;
   run.classify(tasks, mem);
   if (async && (!run.staged.empty() || (run.checks && !async->flags))) return CFSEC_ERR_INVALID_ARG;
   run.size_lanes();
@@ -1502,7 +1667,8 @@ Status LrcEncoder::set_devices(const int* devices, int n) {
 }
 
 Status ECEncoder::reconstruct_batch(cfsec_shard* shards, int n, int nbids, const int* bad, const int* bad_off,
-                                    int mem, bool verify, int* status, const AsyncOut* async, const CrcOut* crc) {
+                                    int mem, bool verify, int* status, const AsyncOut* async, const CrcOut* crc,
+                                    bool bids) {
   // encoder.go:139-144 per bid (initBadShards, engine Reconstruct), then encoder.go:133-137 (Verify)
   if (!shards || !status || !bad_off || nbids < 0) return CFSEC_ERR_INVALID_ARG;
   Slot slot(pool_.get());
@@ -1535,7 +1701,8 @@ Status ECEncoder::reconstruct_batch(cfsec_shard* shards, int n, int nbids, const
     std::vector<StripeTask> tasks;
     engine_->plan_reconstruct_tasks(stripes.data(), (int)stripes.size(), verify, st.data(), 0, 0, &store, &tasks);
     stamp_items(tasks, pos, crc, n);
-    rc = engine_->run_stripes(tasks, mem, async, crc);
+    rc = engine_->run_stripes(tasks, mem, async, crc, /*mix=*/false, /*mix_crc=*/false,
+                              /*mix_sv=*/bids && verify && crc && crc->every && !async);
   }
   for (size_t i = 0; i < pos.size(); ++i) status[pos[i]] = st[i];
   clear_failed_crcs(crc, async, status, nbids, n);
@@ -1543,7 +1710,9 @@ Status ECEncoder::reconstruct_batch(cfsec_shard* shards, int n, int nbids, const
 }
 
 Status LrcEncoder::reconstruct_batch(cfsec_shard* shards, int n, int nbids, const int* bad, const int* bad_off,
-                                     int mem, bool verify, int* status, const AsyncOut* async, const CrcOut* crc) {
+                                     int mem, bool verify, int* status, const AsyncOut* async, const CrcOut* crc,
+                                     bool bids) {
+  const bool mix_sv = bids && verify && crc && crc->every && !async;
   // lrcencoder.go:133-186 per bid, then lrcencoder.go:89-131 (Verify): a local stripe (n = its size)
   // is the local engine alone; a whole stripe is the global engine over its first N+M shards, then
   // each AZ's local engine over that AZ's local stripe -- planned together and run as two phases of
@@ -1598,7 +1767,7 @@ Status LrcEncoder::reconstruct_batch(cfsec_shard* shards, int n, int nbids, cons
     std::vector<StripeTask> tasks;
     local_->plan_reconstruct_tasks(stripes.data(), (int)stripes.size(), verify, st.data(), 0, 0, &store, &tasks);
     stamp_items(tasks, pos, crc, n);
-    const Status rc = local_->run_stripes(tasks, mem, async, crc);
+    const Status rc = local_->run_stripes(tasks, mem, async, crc, /*mix=*/false, /*mix_crc=*/false, mix_sv);
     for (size_t i = 0; i < pos.size(); ++i) status[pos[i]] = st[i];
     clear_failed_crcs(crc, async, status, nbids, n);
     return rc;
@@ -1695,7 +1864,7 @@ Status LrcEncoder::reconstruct_batch(cfsec_shard* shards, int n, int nbids, cons
   ph.reset();
   // the bid: its device, its verify word; rebuilt shards, global or local
   stamp_items(tasks, pos, crc, n, first_local);
-  const Status rc = engine_->run_stripes(tasks, mem, async, crc);
+  const Status rc = engine_->run_stripes(tasks, mem, async, crc, /*mix=*/false, /*mix_crc=*/false, mix_sv);
   // per bid: a Reconstruct error (global, then local) wins over a failed Verify
   std::vector<int> local_err(stripes.size(), CFSEC_OK);
   for (size_t v = 0; v < lp.size(); ++v) {

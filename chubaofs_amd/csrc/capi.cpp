@@ -594,6 +594,16 @@ int cfsec_rs_reconstruct_stripes(cfsec_rs* h, cfsec_shard* shards, int nstripes,
   });
 }
 
+int cfsec_rs_repair_crc_stripes(cfsec_rs* h, cfsec_shard* shards, int nstripes, int mem, int* status,
+                                uint32_t* crcs) {
+  if (!h || nstripes < 0 || (nstripes > 0 && (!shards || !status || !crcs))) return CFSEC_ERR_INVALID_ARG;
+  if (nstripes == 0) return CFSEC_OK;
+  return guarded([&] {
+    auto v = stripe_views(shards, nstripes, h->e->total());
+    return h->e->repair_crc_stripes(v.data(), nstripes, mem, status, crcs);
+  });
+}
+
 int cfsec_rs_reconstruct_some_stripes(cfsec_rs* h, cfsec_shard* shards, int nstripes, const uint8_t* required, int mem,
                                       int* status) {
   if (!h || nstripes < 0 || (nstripes > 0 && (!shards || !status || !required))) return CFSEC_ERR_INVALID_ARG;
@@ -707,16 +717,18 @@ int cfsec_ec_reconstruct_batch_crc(cfsec_ec* h, cfsec_shard* shards, int n, int 
   });
 }
 
-int cfsec_ec_repair_batch_crc(cfsec_ec* h, cfsec_shard* shards, int n, int nbids, const int* bad_idx,
-                              const int* bad_off, int mem, int* status, uint32_t* crcs, const uint32_t* expect,
-                              int* mismatch) {
+extern "C++" {
+namespace {
+// cfsec_ec_repair_batch_crc and, with bids, cfsec_ec_repair_bids_crc: one contract, two sets of launches
+int repair_crc(cfsec_ec* h, cfsec_shard* shards, int n, int nbids, const int* bad_idx, const int* bad_off, int mem,
+               int* status, uint32_t* crcs, const uint32_t* expect, int* mismatch, bool bids) {
   if (!h || nbids < 0 || n <= 0 || (nbids > 0 && (!shards || !status || !bad_off || !crcs)) || (expect && !mismatch))
     return CFSEC_ERR_INVALID_ARG;
   if (!bad_off_valid(nbids, bad_off, bad_idx, mismatch)) return CFSEC_ERR_INVALID_ARG;
   std::memset(crcs, 0, sizeof(uint32_t) * (size_t)nbids * n);
   const cfsec::CrcOut c = crc_out(crcs, nbids, n, true);
   const int rc = guarded([&] {
-    return h->e->reconstruct_batch(shards, n, nbids, bad_idx, bad_off, mem, true, status, nullptr, &c);
+    return h->e->reconstruct_batch(shards, n, nbids, bad_idx, bad_off, mem, true, status, nullptr, &c, bids);
   });
   if (rc != CFSEC_OK || !expect) return rc;
   // downloadShard's check (work_shard_recover.go:654-685) on the words that came back: host arithmetic
@@ -729,6 +741,20 @@ int cfsec_ec_repair_batch_crc(cfsec_ec* h, cfsec_shard* shards, int n, int nbids
     }
   }
   return rc;
+}
+}  // namespace
+}
+
+int cfsec_ec_repair_batch_crc(cfsec_ec* h, cfsec_shard* shards, int n, int nbids, const int* bad_idx,
+                              const int* bad_off, int mem, int* status, uint32_t* crcs, const uint32_t* expect,
+                              int* mismatch) {
+  return repair_crc(h, shards, n, nbids, bad_idx, bad_off, mem, status, crcs, expect, mismatch, /*bids=*/false);
+}
+
+int cfsec_ec_repair_bids_crc(cfsec_ec* h, cfsec_shard* shards, int n, int nbids, const int* bad_idx,
+                             const int* bad_off, int mem, int* status, uint32_t* crcs, const uint32_t* expect,
+                             int* mismatch) {
+  return repair_crc(h, shards, n, nbids, bad_idx, bad_off, mem, status, crcs, expect, mismatch, /*bids=*/true);
 }
 
 int cfsec_ec_encode_batch_crc(cfsec_ec* h, cfsec_shard* shards, int n, int nstripes, int mem, int* status,

@@ -396,6 +396,26 @@ MixPack pack_mix_crc(const StripeTask* const* tasks, uint8_t* const* const* rows
 //   EC6P6         0.79 / 2.38   1.41 / 2.40   3.02 / 2.89   9.00 / 6.29
 // EC6P6 is slower mixed at 256 KiB, so the largest swept length at which no mode loses is 64 KiB; no
 // point between 64 and 256 KiB was swept.
+// The item table of a mixed-plan launch that stores, compares and checksums (gf_mix_sv.hpp): blobnode's
+// repair step, Reconstruct + Verify + every shard's CRC32.  A task is taken when all of these hold: its
+// plan has no dy16 product, 1 .. kLaunchMaxRows inputs and at least one output row (stored or compared:
+// compares() may be true or false -- a bid with exactly N survivors compares nothing and still
+// belongs); 0 < len <= max_len; not half of a split Verify (split == 0); every row checksummed
+// (crc == 3) without an index remap; the only checksummed task of its item (tasks_per_owner, as
+// pack_mix_crc); every word inside [0, nwords); room left below kMixMaxTiles tiles.  Each item carries
+// the plan's nstore and flags[i], the address of task i's Verify word as a number (NULL: zeros).
+// Sizing pass, short buffer, `left` and one coefficient copy per plan as pack_mix.  Host arithmetic only.
+MixPack pack_mix_sv(const StripeTask* const* tasks, uint8_t* const* const* rows, const uint64_t* flags, size_t n,
+                    size_t max_len, size_t nwords, uint64_t tabs, uint64_t crc,
+                    const std::map<int, int>* tasks_per_owner, uint8_t* dst, size_t cap);
+// This route's length limit is kMixMaxLen as well: the same rule (tools/repair_bids_probe.py --sweep, 64
+// scattered bids of ONE shard size and one bad index in HBM, us per bid, mixed / groups):
+//                 16 KiB        64 KiB        256 KiB       1 MiB
+//   EC12P4        1.29 / 3.58   1.55 / 3.67   3.24 / 4.83   9.91 / 8.80
+//   EC6P6         0.86 / 2.27   1.50 / 2.37   3.12 / 3.31   9.59 / 7.93
+//   EC6P10L2      1.27 / 1.67   1.85 / 2.13   4.11 / 3.65   13.75 / 9.46
+// EC6P10L2 is slower mixed at 256 KiB, so the largest swept length at which no mode loses is 64 KiB; no
+// point between 64 and 256 KiB was swept.
 
 // Plans built for one batch call (stable addresses for the tasks that point at them).
 struct PlanStore {
@@ -487,6 +507,12 @@ class RSEngine {
   Status encode_crc_stripes(cfsec_shard* const* stripes, int nst, int mem, int* status, uint32_t* crcs);
   Status verify_stripes(cfsec_shard* const* stripes, int nst, int mem, int* status);
   Status reconstruct_stripes(cfsec_shard* const* stripes, int nst, int mem, bool verify, int* status);
+  //   repair_crc:          reconstruct(verify = true), and crc32.ChecksumIEEE of every shard as it stands
+  //                        afterwards into crcs[s * total() + shard] (host words) for a stripe whose status
+  //                        is OK or CFSEC_ERR_VERIFY, zeros for any other; small stripes of any mix of
+  //                        lengths and erasure patterns share one mixed launch (run_stripes' mix_sv).
+  //                        More than kLaunchMaxRows data shards: CFSEC_ERR_NOT_SUPPORTED.
+  Status repair_crc_stripes(cfsec_shard* const* stripes, int nst, int mem, int* status, uint32_t* crcs);
   //   reconstruct_data:    ReconstructData(shards) (KRS/reedsolomon.go:1377-1397): the missing data
   //                        shards only; small segments of any erasure patterns share one mixed launch
   Status reconstruct_data_stripes(cfsec_shard* const* stripes, int nst, int mem, int* status);
@@ -514,8 +540,11 @@ class RSEngine {
   // mix_crc (synchronous calls): small store-only tasks that checksum every shard share one mixed-plan
   // launch with checksums per part (pack_mix_crc's rule); false: the launch groups and their checksum
   // routes, as every call before the put batches of mixed-size blobs.
+  // mix_sv (synchronous calls): small tasks that store, compare and checksum every shard (a repair
+  // tasklet's bids) share one mixed-plan launch per part (pack_mix_sv's rule), their Verify words routed
+  // as the groups route theirs; false: the launch groups, as every call before the repair of mixed-size bids.
   Status run_stripes(std::vector<StripeTask>& tasks, int mem, const AsyncOut* async = nullptr,
-                     const CrcOut* crc = nullptr, bool mix = false, bool mix_crc = false);
+                     const CrcOut* crc = nullptr, bool mix = false, bool mix_crc = false, bool mix_sv = false);
   // Plan of a Reconstruct (+ Verify) over the present shards; data_only: of a ReconstructData.
   Status plan_stripe(const std::vector<bool>& present, bool verify, StripePlan* plan,
                      const ExtraRows* extra = nullptr, bool data_only = false);
@@ -579,7 +608,7 @@ class RSEngine {
   DeviceContext* ctx_ = nullptr;
   std::vector<DeviceContext*> devs_;  // batch devices, ctx_ first
   Status run_device(std::vector<StripeTask*>& tasks, int mem, DeviceContext* ctx, const AsyncOut* async,
-                    const CrcOut* crc, bool mix, bool mix_crc);
+                    const CrcOut* crc, bool mix, bool mix_crc, bool mix_sv);
 };
 
 // The way a single-stripe call (RSEngine::run) takes, from facts gathered before anything is queued:
@@ -647,9 +676,11 @@ class ECEncoder {
   // async (device memory, asynchronous on async->stream): status[b] gets the planning result at
   // return; a Verify mismatch ORs 1 into async->flags[b] when the stream gets there.
   // crc: the rebuilt shards' checksums into crc->words[b * n + shard] (other words untouched).
+  // bids (with crc->every, synchronous): a tasklet of bids of mixed sizes -- the small bids share one
+  // mixed launch that stores, compares and checksums (run_stripes' mix_sv); same results.
   virtual Status reconstruct_batch(cfsec_shard* shards, int n, int nbids, const int* bad, const int* bad_off,
                                    int mem, bool verify, int* status, const AsyncOut* async = nullptr,
-                                   const CrcOut* crc = nullptr);
+                                   const CrcOut* crc = nullptr, bool bids = false);
   // Encode over a batch of stripes of n shards each (access puts, stream_put.go:104-143), with
   // the Config's EnableVerify; status[s] as Encode would return it.
   // crc: every shard's checksum after the Encode into crc->words[s * n + shard].
@@ -689,7 +720,7 @@ class LrcEncoder : public ECEncoder {
   Status set_devices(const int* devices, int n) override;
   Status reconstruct_batch(cfsec_shard* shards, int n, int nbids, const int* bad, const int* bad_off, int mem,
                            bool verify, int* status, const AsyncOut* async = nullptr,
-                           const CrcOut* crc = nullptr) override;
+                           const CrcOut* crc = nullptr, bool bids = false) override;
   Status encode_batch(cfsec_shard* shards, int n, int nstripes, int mem, int* status,
                       const AsyncOut* async = nullptr, const CrcOut* crc = nullptr, bool blobs = false) override;
   Status reconstruct_data_batch(cfsec_shard* shards, int n, int nitems, const int* bad, const int* bad_off, int mem,

@@ -129,6 +129,12 @@ hipError_t launch_mix(const uint8_t* table, uint32_t ntiles, hipStream_t stream)
 // pack_mix_crc, engine.hpp), whose head names the CRC table block (crc_device_tables) and the checksum
 // words; each row's word is XOR-accumulated, so the caller zeroes the words first.
 hipError_t launch_mix_crc(const uint8_t* table, uint32_t ntiles, hipStream_t stream);
+// The same again with Verify in it (gf_mix_sv.hip): of an item's output rows the first nstore are
+// stored, the rest compared with the shards' own bytes -- a mismatch stores 1 into the item's Verify
+// word, whose address the table holds (device memory or page-locked host memory the device addresses;
+// the caller zeroes it) -- and a compared row's checksum is that of the shard as it stands.  `table` is
+// the device copy of gf_mix_sv.hpp's table (packed by pack_mix_sv, engine.hpp).
+hipError_t launch_mix_sv(const uint8_t* table, uint32_t ntiles, hipStream_t stream);
 
 // launch_dy16_repair's decisions, the same way: per job the table launch, per run the affine
 // bit-sliced prefix and the dyadic tail.

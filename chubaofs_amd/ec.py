@@ -184,6 +184,16 @@ class Encoder:
         mismatch[b] is then the lowest index of a survivor (a shard outside badIdx[b]) whose checksum
         differs, or -1.  The check runs after Reconstruct: a bid with mismatch[b] >= 0 was rebuilt
         from a corrupt survivor and is to be discarded.  Returns (status, crcs, mismatch)."""
+        return self._repair(self._L.cfsec_ec_repair_batch_crc, bids, badIdx, expect)
+
+    def RepairBids(self, bids, badIdx, expect=None):
+        """RepairBatch for a tasklet whose bids differ in size (cfsec_ec_repair_bids_crc): the same
+        statuses, checksums and mismatch indices, but the bids of up to 64 KiB per shard, two or more,
+        share one kernel launch that rebuilds, compares and checksums them, whatever their sizes and
+        bad sets.  Returns (status, crcs, mismatch)."""
+        return self._repair(self._L.cfsec_ec_repair_bids_crc, bids, badIdx, expect)
+
+    def _repair(self, fn, bids, badIdx, expect):
         if len(bids) != len(badIdx):
             raise ValueError("one bad-index list per bid")
         if expect is not None and len(expect) != len(bids):
@@ -204,8 +214,7 @@ class Encoder:
             if any(len(e) != n for e in expect):
                 raise ValueError("n expected checksums per bid")
             exp = (ctypes.c_uint32 * max(len(bids) * n, 1))(*[int(w) & 0xFFFFFFFF for e in expect for w in e])
-        st = self._L.cfsec_ec_repair_batch_crc(self._h, bm.arr, n, len(bids), bad, offs, bm.mem, status, words, exp,
-                                               mism)
+        st = fn(self._h, bm.arr, n, len(bids), bad, offs, bm.mem, status, words, exp, mism)
         bm.writeback()
         _lib.check(st)
         nb = len(bids)

@@ -182,6 +182,22 @@ class ReedSolomon:
         empty) are replaced in the lists by the rebuilt shards.  Per-stripe status codes."""
         return self._stripes(self._L.cfsec_rs_reconstruct_stripes, stripes, True, int(verify))
 
+    def RepairCRCStripes(self, stripes):
+        """ReconstructStripes(verify=True), and crc32.ChecksumIEEE of every shard of every stripe as it
+        stands afterwards, survivors and rebuilt shards (cfsec_rs_repair_crc_stripes): small stripes of any
+        mix of lengths and missing sets share one kernel launch that rebuilds, compares and checksums
+        them.  Returns (per-stripe status codes, per stripe its total_shards checksums; all zero for a
+        stripe whose status is neither 0 nor ErrVerify)."""
+        n = self.total_shards
+        bm = BatchMarshal(stripes, n, fill=True)
+        status = (ctypes.c_int * max(len(stripes), 1))()
+        words = (ctypes.c_uint32 * max(len(stripes) * n, 1))()
+        st = self._L.cfsec_rs_repair_crc_stripes(self._h, bm.arr, len(stripes), bm.mem, status, words)
+        bm.writeback()
+        _lib.check(st)
+        return ([int(status[i]) for i in range(len(stripes))],
+                [[int(words[s * n + i]) for i in range(n)] for s in range(len(stripes))])
+
     def ReconstructDataStripes(self, stripes):
         """ReconstructData of every stripe in one call: the missing data shards only (missing parity
         stays missing); small segments of any mix of erasure patterns and lengths share one kernel

@@ -350,6 +350,23 @@ func (e *ErrCrcNotMatch) Error() string {
 // discarded, exactly as one whose download check failed.
 func (e *ECEncoder) RepairBatch(bids [][][]byte, badIdx [][]int, expect [][]uint32) (errs []error, crcs [][]uint32,
 	check []error, err error) {
+	return e.repair(bids, badIdx, expect, false)
+}
+
+// RepairBids is RepairBatch for a tasklet whose bids differ in size (the bids are whatever blobs lived on
+// the broken disk; a blob smaller than the blob size is one stripe of its own shard size): the same
+// errors, checksums and checks, but the bids of up to 64 KiB per shard, two or more, share one kernel
+// launch that rebuilds, compares and checksums them, whatever their sizes and bad sets
+// (cfsec_ec_repair_bids_crc).  Call it for a tasklet of 16 or more bids that differ in size; smaller
+// tasklets were not measured, and a tasklet of equal-size bids is served by RepairBatch.
+func (e *ECEncoder) RepairBids(bids [][][]byte, badIdx [][]int, expect [][]uint32) (errs []error, crcs [][]uint32,
+	check []error, err error) {
+	return e.repair(bids, badIdx, expect, true)
+}
+
+// mixed: cfsec_ec_repair_bids_crc, else cfsec_ec_repair_batch_crc
+func (e *ECEncoder) repair(bids [][][]byte, badIdx [][]int, expect [][]uint32, mixed bool) (errs []error,
+	crcs [][]uint32, check []error, err error) {
 	if len(bids) != len(badIdx) || (expect != nil && len(expect) != len(bids)) {
 		return nil, nil, nil, errInvalidArg
 	}
@@ -392,6 +409,10 @@ func (e *ECEncoder) RepairBatch(bids [][][]byte, badIdx [][]int, expect [][]uint
 		wp = &want[0]
 	}
 	st := callVec(flat, func(v *C.cfsec_shard, _ C.int) C.int {
+		if mixed {
+			return C.cfsec_ec_repair_bids_crc(e.h, v, C.int(n), C.int(len(bids)), bp, &off[0], C.CFSEC_MEM_HOST,
+				&status[0], &words[0], wp, &mismatch[0])
+		}
 		return C.cfsec_ec_repair_batch_crc(e.h, v, C.int(n), C.int(len(bids)), bp, &off[0], C.CFSEC_MEM_HOST,
 			&status[0], &words[0], wp, &mismatch[0])
 	})

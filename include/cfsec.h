@@ -252,6 +252,17 @@ int cfsec_rs_verify_stripes(cfsec_rs* h, cfsec_shard* shards, int nstripes, int 
  * false).  Bit-exact with the two calls on any input, consistent or not. */
 int cfsec_rs_reconstruct_stripes(cfsec_rs* h, cfsec_shard* shards, int nstripes, int verify, int mem,
                                  int* status);
+/* cfsec_rs_reconstruct_stripes(verify = 1) with every shard's checksum, the heterogeneous sibling of
+ * cfsec_rs_repair_crc_batch (blobnode's repair step, work_shard_recover.go:708-771, 335-342): crcs is a
+ * host array of nstripes * (data+parity) words; crcs[s * total + i] = crc32.ChecksumIEEE of shard i of
+ * stripe s as it stands in memory after the call -- survivors and rebuilt shards -- for a stripe whose
+ * status is CFSEC_OK or CFSEC_ERR_VERIFY, all-zero words for any other.  Stripes of up to 64 KiB per
+ * shard, two or more, of any mix of lengths, byte alignments and missing sets run as ONE launch that
+ * rebuilds, compares and checksums them; longer stripes, a lone small one and 16 x 16
+ * dyadic repairs take the launches of cfsec_rs_reconstruct_stripes and a separate checksum pass.
+ * CFSEC_MIX_MAX_LEN as below.  CFSEC_ERR_NOT_SUPPORTED with more than 32 data shards. */
+int cfsec_rs_repair_crc_stripes(cfsec_rs* h, cfsec_shard* shards, int nstripes, int mem, int* status,
+                                uint32_t* crcs);
 /* reedsolomon.ReconstructData per stripe (KRS/reedsolomon.go:1377-1397, 1407-1552 with dataOnly):
  * the missing data shards only (cap >= shard size, len = shard size afterwards); missing parity
  * shards stay missing, a stripe with no data shard missing is a no-op.  status[s] is what
@@ -349,6 +360,25 @@ int cfsec_ec_encode_blobs_crc(cfsec_ec* h, cfsec_shard* shards, int n, int nstri
 int cfsec_ec_repair_batch_crc(cfsec_ec* h, cfsec_shard* shards, int n, int nbids, const int* bad_idx,
                               const int* bad_off, int mem, int* status, uint32_t* crcs, const uint32_t* expect,
                               int* mismatch);
+/* cfsec_ec_repair_batch_crc for a tasklet whose bids differ in size (the bids are whatever blobs lived
+ * on the broken disk: most are smaller than the blob size, one stripe each of its own shard size): the
+ * same contract word for word -- RS and LRC modes, status[], crcs kept for CFSEC_OK and
+ * CFSEC_ERR_VERIFY, expect / mismatch -- but the bids of up to 64 KiB per shard, two or more, share ONE
+ * launch that rebuilds, compares and checksums them (the mixed-plan launch with Verify, DESIGN.md
+ * §4.5), whatever their sizes, byte alignments and bad sets, where cfsec_ec_repair_batch_crc takes a
+ * product launch per bad set and a checksum launch per distinct length.  A compared survivor's word is
+ * the checksum of the shard as it stands in memory, corrupt or not.  An LRC bid with no bad local
+ * shard has its local parities compared and checksummed in that launch too.  These keep the routes of
+ * cfsec_ec_repair_batch_crc, with the same results: longer bids and a lone small one; bids whose
+ * repair is the 16 x 16 dyadic product (most repairs of EC16P20L2); LRC bids with a bad local shard
+ * (two checksummed passes per bid).  Synchronous only.  CFSEC_MIX_MAX_LEN as for
+ * cfsec_rs_reconstruct_data_stripes.  Call it for a tasklet of 16 or more bids that differ in size
+ * (measured on one MI355X: 2.2-6.8 times faster per bid in HBM, 2.0-3.2 times on page-locked shards,
+ * DESIGN.md §4.5); smaller tasklets were not measured, and a tasklet of equal-size bids is served by
+ * cfsec_ec_repair_batch_crc. */
+int cfsec_ec_repair_bids_crc(cfsec_ec* h, cfsec_shard* shards, int n, int nbids, const int* bad_idx,
+                             const int* bad_off, int mem, int* status, uint32_t* crcs, const uint32_t* expect,
+                             int* mismatch);
 /* Asynchronous forms of the two batch calls above, for device memory on the handle's (first) device:
  * the call plans the batch, enqueues its kernels on `stream` (hipStream_t; NULL = the legacy default
  * stream) and returns without waiting, so a caller overlaps the next tasklet's planning with this
