@@ -20,6 +20,7 @@
 #include "crc_pow.hpp"
 #include "gf_mix_crc.hpp"
 #include "gf_mix_sv.hpp"
+#include "gf_mix_sv16.hpp"
 
 namespace cfsec {
 namespace {
@@ -654,6 +655,158 @@ MixPack pack_mix_sv(const StripeTask* const* tasks, uint8_t* const* const* rows,
   return pk;
 }
 
+MixPack pack_mix_sv16(const StripeTask* const* tasks, uint8_t* const* const* rows, const uint64_t* flags, size_t n,
+                      size_t max_len, size_t nwords, uint64_t tabs, uint64_t crc,
+                      const std::map<int, int>* tasks_per_owner, uint8_t* dst, size_t cap) {
+  MixPack pk;
+  // an item's words have one writer: a task is taken when no other task of its item checksums
+  std::map<int, int> counted;
+  if (!tasks_per_owner) {
+    for (size_t i = 0; i < n; ++i)
+      if (tasks[i]->crc) ++counted[tasks[i]->owner];
+    tasks_per_owner = &counted;
+  }
+  // A Dy16Plan output row as a position in the task's rows (plan->in then plan->out), and whether the
+  // launch touches it: the missing data rows and the parity / extra rows with a mask bit.  A parity row
+  // with neither bit is a stand-in among the inputs (checksummed there) or a row of no plan.
+  const auto out_row = [](const StripePlan& p, const Dy16Plan& d, size_t r, size_t* pos) {
+    const int idx = d.rows[r];
+    const bool used = r < (size_t)d.nd || (((d.pstore | d.pcmp) >> (r - d.nd)) & 1u);
+    const size_t o = std::find(p.out.begin(), p.out.end(), idx) - p.out.begin();
+    *pos = p.in.size() + o;
+    return used && o < p.out.size();
+  };
+  // the sizing pass: which tasks go in, their tiles and rows, one coefficient block per plan
+  std::map<const StripePlan*, uint32_t> coef_at;  // plan -> byte offset within the coefficient area
+  std::vector<size_t> take;
+  size_t nrows = 0, ncoef = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const StripeTask& t = *tasks[i];
+    const StripePlan& p = *t.plan;
+    const Dy16Plan* d = p.dy16.get();
+    const uint64_t tiles = ((uint64_t)t.len + kMixTile - 1) / kMixTile;
+    bool ok = d && p.in.size() == (size_t)kMixSv16In && d->nd >= 0 && d->nd <= 4 && (d->e == 0 || d->e == 2) &&
+              d->rows.size() == (size_t)(d->nd + 20 + d->e) && d->coef.rows == 20 + d->e + d->nd && d->coef.cols == 16 &&
+              t.len > 0 && t.len <= max_len && t.split == 0 && t.crc == 3 && !t.crc_map &&
+              tiles <= kMixMaxTiles - pk.tiles;
+    if (ok) {
+      const auto owner = tasks_per_owner->find(t.owner);
+      ok = owner != tasks_per_owner->end() && owner->second == 1;
+    }
+    int miss = 0;
+    for (int c = 0; ok && c < 16; ++c) {  // src[] names every input once, the nd missing rows in order
+      const int s = d->src[c];
+      ok = s < 16 ? s == c - miss : (s - 16 == miss && miss < d->nd && d->rows[miss] == c);
+      miss += s >= 16;
+    }
+    ok = ok && miss == d->nd;
+    const auto word_ok = [&](int shard) {  // every word inside the call's words
+      const int64_t w = t.crc_word + shard;
+      return w >= 0 && (uint64_t)w < nwords && (uint64_t)w < kMixNoWord;
+    };
+    for (size_t c = 0; ok && c < p.in.size(); ++c) ok = word_ok(p.in[c]);
+    for (size_t r = 0; ok && r < d->rows.size(); ++r) {
+      size_t pos;
+      const bool untouched = r >= (size_t)d->nd && !(((d->pstore | d->pcmp) >> (r - d->nd)) & 1u);
+      ok = untouched || (out_row(p, *d, r, &pos) && word_ok(d->rows[r]));  // a touched row is one of plan->out
+    }
+    if (!ok) {
+      pk.left.push_back(i);
+      continue;
+    }
+    take.push_back(i);
+    pk.tiles += (uint32_t)tiles;
+    nrows += kMixSv16In + d->rows.size();
+    if (coef_at.emplace(&p, (uint32_t)ncoef).second) ncoef += align_up(d->coef.v.size(), 16);
+  }
+  pk.items = (uint32_t)take.size();
+  pk.plans = (uint32_t)coef_at.size();
+  MixCrcHead h{};
+  h.nitems = pk.items;
+  h.ntiles = pk.tiles;
+  h.nplans = pk.plans;
+  h.tabs = tabs;
+  h.crc = crc;
+  h.items_off = (uint32_t)sizeof(MixCrcHead);
+  const size_t rows_off = h.items_off + (size_t)pk.items * sizeof(MixSv16Item);
+  const size_t words_off = rows_off + nrows * 8;
+  const size_t map_off = words_off + nrows * 4;
+  const size_t coef_off = align_up(map_off + (size_t)pk.tiles * 4, 16);
+  pk.bytes = coef_off + ncoef;
+  if (pk.bytes > 0xFFFFFFFFu) {  // 32-bit offsets: never with kMixMaxTiles tiles of rows a launch addresses
+    pk = MixPack();
+    for (size_t i = 0; i < n; ++i) pk.left.push_back(i);
+    return pk;
+  }
+  h.rows_off = (uint32_t)rows_off;
+  h.words_off = (uint32_t)words_off;
+  h.map_off = (uint32_t)map_off;
+  h.coef_off = (uint32_t)coef_off;
+  h.bytes = (uint32_t)pk.bytes;
+  if (!dst || cap < pk.bytes || pk.items == 0) return pk;
+  static const MixCrcPow2 pow2;
+  const CrcPowTables& pw = crc_pow_tables();
+  std::memcpy(h.xpow2, pow2.v, sizeof h.xpow2);
+  std::memcpy(dst, &h, sizeof h);
+  uint8_t* item = dst + h.items_off;
+  uint64_t* row = reinterpret_cast<uint64_t*>(dst + h.rows_off);
+  uint32_t* word = reinterpret_cast<uint32_t*>(dst + h.words_off);
+  uint32_t* tile_item = reinterpret_cast<uint32_t*>(dst + h.map_off);
+  // Slot order (gf_dy16.hip to_slot_order): the plan's inputs come in first-present order -- the
+  // present data rows, then the stand-in parities -- and Dy16Plan::src[i] is data row i's place there
+  // (16 + j: missing row j); slot i takes input col[i], the j-th stand-in for missing row j.
+  const auto slot_cols = [](const Dy16Plan& d, int (&col)[16]) {
+    for (int i = 0; i < 16; ++i) col[i] = d.src[i] < 16 ? d.src[i] : (16 - d.nd) + (d.src[i] - 16);
+  };
+  uint32_t tile = 0, at = 0;
+  for (size_t j = 0; j < take.size(); ++j) {
+    const StripeTask& t = *tasks[take[j]];
+    const StripePlan& p = *t.plan;
+    const Dy16Plan& d = *p.dy16;
+    MixSv16Item it{};
+    it.len = t.len;
+    it.flag = flags ? flags[take[j]] : 0;
+    it.coef = h.coef_off + coef_at[&p];
+    it.rows = at;
+    it.tile0 = tile;
+    it.ntiles = (uint32_t)((t.len + kMixTile - 1) / kMixTile);
+    it.fin = crc_shift_ones_of((uint64_t)t.len >> 40 ? crc_xpow((int64_t)(8 * (uint64_t)t.len)) : crc_xpow8((int64_t)t.len));
+    it.gend = pw.neg[(uint64_t)it.ntiles * kMixTile - t.len];
+    it.pstore = d.pstore;
+    it.pcmp = d.pcmp;
+    it.nd = (uint8_t)d.nd;
+    it.e = (uint8_t)d.e;
+    for (int q = 0; q < d.nd; ++q) it.src[q] = (uint8_t)d.rows[q];
+    std::memcpy(item + j * sizeof it, &it, sizeof it);
+    int col[16];
+    slot_cols(d, col);
+    for (int s = 0; s < 16; ++s, ++at) {
+      row[at] = (uint64_t)(uintptr_t)rows[take[j]][col[s]];
+      word[at] = (uint32_t)(t.crc_word + p.in[col[s]]);
+    }
+    for (size_t r = 0; r < d.rows.size(); ++r, ++at) {
+      size_t pos;
+      const bool used = out_row(p, d, r, &pos);
+      row[at] = used ? (uint64_t)(uintptr_t)rows[take[j]][pos] : 0;
+      word[at] = used ? (uint32_t)(t.crc_word + d.rows[r]) : kMixNoWord;
+    }
+    for (uint32_t q = 0; q < it.ntiles; ++q) tile_item[tile++] = (uint32_t)j;
+  }
+  std::memset(dst + map_off + (size_t)pk.tiles * 4, 0, coef_off - (map_off + (size_t)pk.tiles * 4));
+  for (const auto& kv : coef_at) {
+    const Dy16Plan& d = *kv.first->dy16;
+    const size_t sz = d.coef.v.size();
+    uint8_t* c = dst + h.coef_off + kv.second;
+    std::memcpy(c, d.coef.v.data(), sz);
+    int col[16];
+    slot_cols(d, col);
+    for (int q = 0; q < d.nd; ++q)  // the decode rows' columns in slot order
+      for (int s = 0; s < 16; ++s) c[(20 + d.e + q) * 16 + s] = d.coef.at(20 + d.e + q, col[s]);
+    std::memset(c + sz, 0, align_up(sz, 16) - sz);
+  }
+  return pk;
+}
+
 void partition_stripes(const uint64_t* bytes, int n, int ndev, int* dev) {
   // Stripe i goes to the device whose share of the byte total holds the midpoint of stripe i's
   // bytes: contiguous, non-decreasing runs whose loads differ by at most one stripe's bytes.
@@ -1250,7 +1403,7 @@ struct BatchRun {
   // that store, compare and checksum every shard share one launch per part (launch_mixed's sv form); 0:
   // the groups
   size_t mix_sv_len = 0;
-  enum MixKind { kMix, kMixCrc, kMixSv };
+  enum MixKind { kMix, kMixCrc, kMixSv, kMixSv16 };
 
   Status join(int from, int to) { return lane_wait(ws->ev, lane[from], lane[to]); }
   void classify(const std::vector<StripeTask*>& tasks, int mem);
@@ -1425,7 +1578,18 @@ Status BatchRun::launch_part(const Part& whole, hipStream_t s, bool fuse_crc) {
   bool split = false;
   if (mix_len) st = launch_mixed(whole, s, kMix, &rest, &split);
   else if (mix_crc_len && sums) st = launch_mixed(whole, s, kMixCrc, &rest, &split);
-  else if (mix_sv_len && sums) st = launch_mixed(whole, s, kMixSv, &rest, &split);
+  else if (mix_sv_len && sums) {
+    st = launch_mixed(whole, s, kMixSv, &rest, &split);
+    // the 16 + 20 code's bids, which that launch refuses for their dy16 product: a launch of their own
+    // (gf_mix_sv16.hip), on the same terms -- two or more, the rest to the groups
+    Part rest16;
+    bool split16 = false;
+    if (st == CFSEC_OK) st = launch_mixed(split ? rest : whole, s, kMixSv16, &rest16, &split16);
+    if (split16) {
+      rest = std::move(rest16);
+      split = true;
+    }
+  }
   if (st != CFSEC_OK) return st;
   const Part& part = split ? rest : whole;
   std::vector<Group> groups;
@@ -1472,11 +1636,11 @@ Status BatchRun::launch_part(const Part& whole, hipStream_t s, bool fuse_crc) {
 
 // The tasks of a part the item table takes (pack_mix; kMixCrc: pack_mix_crc, whose launch also
 // checksums every row of its items into the call's words; kMixSv: pack_mix_sv, whose launch compares
-// rows too), when there are at least two, as one mixed launch on stream s: the table packed into the
+// rows too; kMixSv16: pack_mix_sv16, the same for the 16 + 20 code's dy16 plans), when there are at least two, as one mixed launch on stream s: the table packed into the
 // lane's page-locked buffer, one copy to the device, the launch.  *rest gets the other tasks (*split
 // true), which go through the groups and the separate checksum pass as before; with fewer than two
 // takers nothing is launched and *split stays false.
-// kMixSv: a taker's Verify word is routed as the groups route theirs -- with fdirect the item's own word
+// kMixSv, kMixSv16: a taker's Verify word is routed as the groups route theirs -- with fdirect the item's own word
 // (recorded as written directly), otherwise a per-task word and the gather.
 Status BatchRun::launch_mixed(const Part& part, hipStream_t s, MixKind kind, Part* rest, bool* split) {
   HostTimer mt("      launch_mixed");
@@ -1486,11 +1650,13 @@ Status BatchRun::launch_mixed(const Part& part, hipStream_t s, MixKind kind, Par
     const Status e = hip_status(crc_device_tables(&tabs), "crc_device_tables");
     if (e != CFSEC_OK) return e;
   }
-  std::vector<uint64_t> fword;  // kMixSv: the address of every taker's Verify word
+  const bool sv = kind == kMixSv || kind == kMixSv16;
+  std::vector<uint64_t> fword;  // kMixSv, kMixSv16: the address of every taker's Verify word
   const auto pack = [&](uint8_t* dst, size_t cap) {
-    if (kind == kMixSv)
-      return pack_mix_sv(part.tasks.data(), part.rows.data(), fword.empty() ? nullptr : fword.data(), n, mix_sv_len,
-                         crc->n, (uint64_t)(uintptr_t)tabs, (uint64_t)(uintptr_t)dcrc, &tasks_per_owner, dst, cap);
+    if (sv)
+      return (kind == kMixSv ? pack_mix_sv : pack_mix_sv16)(
+          part.tasks.data(), part.rows.data(), fword.empty() ? nullptr : fword.data(), n, mix_sv_len, crc->n,
+          (uint64_t)(uintptr_t)tabs, (uint64_t)(uintptr_t)dcrc, &tasks_per_owner, dst, cap);
     return kind == kMixCrc ? pack_mix_crc(part.tasks.data(), part.rows.data(), n, mix_crc_len, crc->n,
                                           (uint64_t)(uintptr_t)tabs, (uint64_t)(uintptr_t)dcrc, &tasks_per_owner, dst,
                                           cap)
@@ -1498,7 +1664,7 @@ Status BatchRun::launch_mixed(const Part& part, hipStream_t s, MixKind kind, Par
   };
   const MixPack sz = pack(nullptr, 0);
   if (sz.items < 2) return CFSEC_OK;
-  if (kind == kMixSv) {
+  if (sv) {
     std::vector<char> is_left(n, 0);
     for (size_t i : sz.left) is_left[i] = 1;
     fword.assign(n, 0);
@@ -1527,13 +1693,15 @@ Status BatchRun::launch_mixed(const Part& part, hipStream_t s, MixKind kind, Par
   if (st == CFSEC_OK) st = hip_status(hipEventRecord(ws->mix_ev[slot], s), "hipEventRecord(mix table)");
   ws->mix_busy[slot] = true;
   if (st == CFSEC_OK)
-    st = kind == kMixSv    ? hip_status(launch_mix_sv(ws->dmix[slot], pk.tiles, s), "launch_mix_sv")
+    st = kind == kMixSv16  ? hip_status(launch_mix_sv16(ws->dmix[slot], pk.tiles, s), "launch_mix_sv16")
+         : kind == kMixSv  ? hip_status(launch_mix_sv(ws->dmix[slot], pk.tiles, s), "launch_mix_sv")
          : kind == kMixCrc ? hip_status(launch_mix_crc(ws->dmix[slot], pk.tiles, s), "launch_mix_crc")
                            : hip_status(launch_mix(ws->dmix[slot], pk.tiles, s), "launch_mix");
   const char* tr = std::getenv("CFSEC_TRACE_MATVEC");
   if (tr && tr[0] && tr[0] != '0')
     std::fprintf(stderr, "cfsec: %s items=%u tiles=%u plans=%u\n",
-                 kind == kMixSv ? "mixsv" : kind == kMixCrc ? "mixcrc" : "mix", pk.items, pk.tiles, pk.plans);
+                 kind == kMixSv16 ? "mixsv16" : kind == kMixSv ? "mixsv" : kind == kMixCrc ? "mixcrc" : "mix", pk.items,
+                 pk.tiles, pk.plans);
   for (size_t i : pk.left) {
     rest->tasks.push_back(part.tasks[i]);
     rest->rows.push_back(part.rows[i]);

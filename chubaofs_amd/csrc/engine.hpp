@@ -416,6 +416,22 @@ MixPack pack_mix_sv(const StripeTask* const* tasks, uint8_t* const* const* rows,
 //   EC6P10L2      1.27 / 1.67   1.85 / 2.13   4.11 / 3.65   13.75 / 9.46
 // EC6P10L2 is slower mixed at 256 KiB, so the largest swept length at which no mode loses is 64 KiB; no
 // point between 64 and 256 KiB was swept.
+// The item table of the mixed-plan repair launch of the 16 + 20 code (gf_mix_sv16.hpp): the tasks
+// pack_mix_sv refuses for their dy16 product.  A task is taken when all of these hold: its plan carries
+// a Dy16Plan (nd <= 4 missing data rows, 0 or 2 extra rows, src[] consistent with rows[]) and has 16
+// inputs; 0 < len <= max_len; split == 0; crc == 3 without an index remap; the only checksummed task of
+// its item (tasks_per_owner, as pack_mix_crc); every word inside [0, nwords); room left below
+// kMixMaxTiles tiles.  Per item: len, tiles, the CRC constants, flags[i] (the address of task i's Verify
+// word, NULL: zeros), the plan's nd, e, pstore, pcmp and src[j] = the data row of missing row j; the 16
+// input addresses in data-row slot order (gf_dy16.hip to_slot_order), then the addresses of
+// Dy16Plan::rows; parallel to them the word each row writes -- kMixNoWord for a parity row with neither
+// mask bit (a stand-in already among the inputs, or a row nobody asked for), so every shard of the bid
+// has exactly one writer.  One coefficient block per plan (by address): Dy16Plan::coef with the decode
+// rows' columns permuted to slot order.  Sizing pass, short buffer and `left` as pack_mix.  Host
+// arithmetic only.
+MixPack pack_mix_sv16(const StripeTask* const* tasks, uint8_t* const* const* rows, const uint64_t* flags, size_t n,
+                      size_t max_len, size_t nwords, uint64_t tabs, uint64_t crc,
+                      const std::map<int, int>* tasks_per_owner, uint8_t* dst, size_t cap);
 
 // Plans built for one batch call (stable addresses for the tasks that point at them).
 struct PlanStore {

@@ -135,6 +135,12 @@ hipError_t launch_mix_crc(const uint8_t* table, uint32_t ntiles, hipStream_t str
 // the caller zeroes it) -- and a compared row's checksum is that of the shard as it stands.  `table` is
 // the device copy of gf_mix_sv.hpp's table (packed by pack_mix_sv, engine.hpp).
 hipError_t launch_mix_sv(const uint8_t* table, uint32_t ntiles, hipStream_t stream);
+// The same for items of the 16 + 20 code whose plan carries a Dy16Plan (gf_mix_sv16.hip): the missing
+// data rows from their decode rows, then every parity and extra row through the 16x16 dyadic block,
+// stored, compared or dropped by the item's masks, from one read of the 16 inputs.  `table` is the
+// device copy of gf_mix_sv16.hpp's table (packed by pack_mix_sv16, engine.hpp); words and Verify words
+// as launch_mix_sv.
+hipError_t launch_mix_sv16(const uint8_t* table, uint32_t ntiles, hipStream_t stream);
 
 // launch_dy16_repair's decisions, the same way: per job the table launch, per run the affine
 // bit-sliced prefix and the dyadic tail.

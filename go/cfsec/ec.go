@@ -357,7 +357,8 @@ func (e *ECEncoder) RepairBatch(bids [][][]byte, badIdx [][]int, expect [][]uint
 // the broken disk; a blob smaller than the blob size is one stripe of its own shard size): the same
 // errors, checksums and checks, but the bids of up to 64 KiB per shard, two or more, share one kernel
 // launch that rebuilds, compares and checksums them, whatever their sizes and bad sets
-// (cfsec_ec_repair_bids_crc).  Call it for a tasklet of 16 or more bids that differ in size; smaller
+// (cfsec_ec_repair_bids_crc); EC16P20L2's bids with at most 4 missing data shards share a launch of
+// their own, built on the 16 x 16 dyadic product.  Call it for a tasklet of 16 or more bids that differ in size; smaller
 // tasklets were not measured, and a tasklet of equal-size bids is served by RepairBatch.
 func (e *ECEncoder) RepairBids(bids [][][]byte, badIdx [][]int, expect [][]uint32) (errs []error, crcs [][]uint32,
 	check []error, err error) {

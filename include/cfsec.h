@@ -258,8 +258,10 @@ int cfsec_rs_reconstruct_stripes(cfsec_rs* h, cfsec_shard* shards, int nstripes,
  * stripe s as it stands in memory after the call -- survivors and rebuilt shards -- for a stripe whose
  * status is CFSEC_OK or CFSEC_ERR_VERIFY, all-zero words for any other.  Stripes of up to 64 KiB per
  * shard, two or more, of any mix of lengths, byte alignments and missing sets run as ONE launch that
- * rebuilds, compares and checksums them; longer stripes, a lone small one and 16 x 16
- * dyadic repairs take the launches of cfsec_rs_reconstruct_stripes and a separate checksum pass.
+ * rebuilds, compares and checksums them -- RS(16, 20) stripes with at most 4 missing
+ * data shards as one launch of their own, which drives the 16 x 16 dyadic product from the same kind
+ * of item table; longer stripes and a lone small one (of either kind) take the launches of
+ * cfsec_rs_reconstruct_stripes and a separate checksum pass.
  * CFSEC_MIX_MAX_LEN as below.  CFSEC_ERR_NOT_SUPPORTED with more than 32 data shards. */
 int cfsec_rs_repair_crc_stripes(cfsec_rs* h, cfsec_shard* shards, int nstripes, int mem, int* status,
                                 uint32_t* crcs);
@@ -368,10 +370,13 @@ int cfsec_ec_repair_batch_crc(cfsec_ec* h, cfsec_shard* shards, int n, int nbids
  * §4.5), whatever their sizes, byte alignments and bad sets, where cfsec_ec_repair_batch_crc takes a
  * product launch per bad set and a checksum launch per distinct length.  A compared survivor's word is
  * the checksum of the shard as it stands in memory, corrupt or not.  An LRC bid with no bad local
- * shard has its local parities compared and checksummed in that launch too.  These keep the routes of
- * cfsec_ec_repair_batch_crc, with the same results: longer bids and a lone small one; bids whose
- * repair is the 16 x 16 dyadic product (most repairs of EC16P20L2); LRC bids with a bad local shard
- * (two checksummed passes per bid).  Synchronous only.  CFSEC_MIX_MAX_LEN as for
+ * shard has its local parities compared and checksummed in that launch too.  Bids whose repair is the
+ * 16 x 16 dyadic product (the 16 + 20 code with at most 4 missing data shards: most repairs of
+ * EC16P20L2) share a second launch of the same kind, which computes that product from one read of the
+ * bid's 16 inputs (DESIGN.md §4.5 "The 16 + 20 code"); two or more such bids make one, a lone one keeps
+ * the old route.  These keep the routes of cfsec_ec_repair_batch_crc, with the same results: longer
+ * bids and a lone small one; LRC bids with a bad local shard (two checksummed passes per bid).
+ * Synchronous only.  CFSEC_MIX_MAX_LEN as for
  * cfsec_rs_reconstruct_data_stripes.  Call it for a tasklet of 16 or more bids that differ in size
  * (measured on one MI355X: 2.2-6.8 times faster per bid in HBM, 2.0-3.2 times on page-locked shards,
  * DESIGN.md §4.5); smaller tasklets were not measured, and a tasklet of equal-size bids is served by

@@ -19,6 +19,13 @@ each divided by B, for EC12P4, EC6P6 and EC6P10L2, B in {16, 64, 256}, shard siz
 from each other, as separately downloaded shards do.  The shards hold valid codewords, so every Verify
 holds.  The launch counts of the two GPU calls are read from their traces in one extra, untimed call each.
 
+--modes EC16P20L2,EC16P20 times the 16 + 20 code, whose bids take the mixed-plan repair launch that drives
+the 16x16-dyadic product from an item table (gf_mix_sv16.hip): EC16P20L2 with BASELINE configs[3-4]'s bad
+set [0, 1, 16, 17] as the one bad set, EC16P20 (its RS sibling, 36 shards in one AZ; no code mode names it)
+with one bad data shard.  Run in a process of its own with CFSEC_NO_DY16_REPAIR=1 (read once per process),
+no plan carries a dy16 product and the bids_crc column is the generic launch (gf_mix_sv.hip) on the same
+bids: the evidence for or against the dyadic body over the plain one.
+
 --sweep times a tasklet of 64 bids of ONE shard size and one bad index with the mixed launch forced on and
 off (CFSEC_MIX_MAX_LEN) at 16 KiB .. 1 MiB, on cfsec_ec_repair_bids_crc: the table the route's length limit
 is read from (the largest length at which the mixed launch is no slower on the one-size tasklet).
@@ -44,13 +51,24 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from chubaofs_amd import _lib, ec, reedsolomon  # noqa: E402
 from oracle import oracle as O  # noqa: E402
 from oracle.ec_oracle import layout_by_az  # noqa: E402
-from put_blobs_probe import alternate, blob_sizes, tactic, with_limit  # noqa: E402
+from chubaofs_amd.codemode import Tactic  # noqa: E402
+from put_blobs_probe import alternate, blob_sizes, with_limit  # noqa: E402
+from put_blobs_probe import tactic as mode_tactic  # noqa: E402
+
+
+def tactic(name):
+    return Tactic(16, 20, 0, 1, 16, 0, 0) if name == "EC16P20" else mode_tactic(name)
+
+
+def one_bad(t):
+    """The bad set of a disk repair: one data shard; for EC16P20L2 the set the project benchmarks (C5)."""
+    return [0, 1, 16, 17] if (t.N, t.M, t.L) == (16, 20, 2) else [1]
 
 
 def bad_sets(t, B, distinct, rng):
     """One bad data shard for every bid, or per bid one of 16 distinct sets of 1 .. min(M, 3) global shards."""
     if not distinct:
-        return [[1]] * B
+        return [one_bad(t)] * B
     sets = set()
     while len(sets) < 16:
         nb = int(rng.integers(1, min(t.M, 3) + 1))
@@ -185,7 +203,7 @@ class Tasklet:
             f.seek(0)
             ln = f.read().decode().splitlines()
         count = lambda *p: sum(1 for x in ln if any(x.startswith(q) for q in p))  # noqa: E731
-        return (count("cfsec: mixsv "), count("cfsec: matvec ", "cfsec: dy16"),
+        return (count("cfsec: mixsv ", "cfsec: mixsv16 "), count("cfsec: matvec ", "cfsec: dy16"),
                 count("cfsec: crc route", "cfsec: crc sv", "cfsec: bs launch"), count("cfsec: crc32 "))
 
 
@@ -212,7 +230,7 @@ def main():
             t = tactic(name)
             enc = ec.NewEncoder(ec.Config(CodeMode=t))
             for S in (16 << 10, 64 << 10, 256 << 10, 1 << 20):
-                b = Tasklet(enc, t, [S] * 64, [[1]] * 64, pinned=False)
+                b = Tasklet(enc, t, [S] * 64, [one_bad(t)] * 64, pinned=False)
                 mixed, groups = alternate([with_limit(1 << 30, b.bids), with_limit(0, b.bids)], a.warmup, a.reps)
                 rows.append(dict(sweep=True, mode=name, shard=S, mixed_us=mixed, groups_us=groups))
                 print("%-9s %8d %10.2f %10.2f" % (name, S, mixed, groups), flush=True)
